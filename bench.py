@@ -3,7 +3,20 @@
 "Lloyd point-iters/sec (whole node) + achieved HBM GB/s, 100M files d=16 k=64".
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU)
+
+A plain run does only what the headline figure needs: set-up (generation,
+seeding), W warmup steps, exactly K timed steps, the JSON line.  `--full`
+adds everything else the benchmark measures: the CPU baseline of the leg
+(`cpu_baseline`), the repeated, steady-state seeding (`seed_warm_s`) and, for
+config 3 on one GPU, the other configs' legs under `secondary`
+(`--no-cpu-baseline` / `--no-secondary` take single parts out again).
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path
+returned in its last step as DIR/<name>.npy (float64; see dump_outputs): with
+the same arguments the inputs are identical from run to run, so two builds
+can be compared output for output.
 
 A step = one full Lloyd iteration of src/kmeans_plusplus.py:31-48 over the
 whole sharded data set: fused assign+update kernels on every rank, one RCCL
@@ -33,9 +46,9 @@ figure, n_local * (4*d + 4) bytes (read the fp32 point, write its int32 label),
 over the same time is `effective_achieved` / `effective_frac` — above 1,
 because the kernel does not need those bytes.
 
-cpu_baseline: the NumPy oracle (restatement of the reference, 1 core — NumPy
-ufuncs are single-threaded) timed on this host on a 1M-row sample of the
-same data, rank 0 at N=1 only.
+cpu_baseline (`--full`): the NumPy oracle (restatement of the reference, 1
+core — NumPy ufuncs are single-threaded) timed on this host on a 1M-row
+sample of the same data, rank 0 at N=1 only.
 """
 from __future__ import annotations
 
@@ -67,6 +80,47 @@ EVENTS_PER_FILE = 168.1  # mean of the simulator model (sum of category rates x 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md chip table (spec)
 MFMA_F16_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: BF16/FP16 MFMA ~2.5 PF dense
 METRIC = "Lloyd point-iters/sec (whole node) + achieved HBM GB/s, 100M files d=16 k=64"
+DUMP_MAX_BYTES = 64 * 2 ** 20  # --dump-outputs: all files together
+DUMP_SAMPLE_VALUES = 2_000_000  # values kept of a per-row output that has more
+DUMP_SAMPLE_SEED = 0xD0
+
+
+def sample_rows(n: int, width: int = 1):
+    """--dump-outputs: the rows written of a per-row output of n rows x width
+    values: all of them (None) up to DUMP_SAMPLE_VALUES values, else a fixed
+    sample (sorted, distinct draws of a generator of its own, seeded with
+    DUMP_SAMPLE_SEED: the same rows for the same shape in every run and
+    build)."""
+    import numpy as np
+
+    m = DUMP_SAMPLE_VALUES // max(width, 1)
+    if n <= m:
+        return None
+    return np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, n, m))
+
+
+def sampled(name: str, a) -> dict:
+    """A per-row output for dump_outputs: {name: a} when small, else the
+    sampled rows and, as <name>_rows, their indices."""
+    rows = sample_rows(a.shape[0], int(a.size // max(a.shape[0], 1)))
+    if rows is None:
+        return {name: a}
+    return {name: a[rows], name + "_rows": rows}
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: write each array as path/<name>.npy in float64 (the
+    integer outputs - labels, counts, row indices - are far below 2^53, so
+    the conversion is exact).  Refuses more than DUMP_MAX_BYTES in all."""
+    import numpy as np
+
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(d: int, k: int, seed: int, rows: int = 1_000_000, iters: int = 2) -> dict:
@@ -139,6 +193,11 @@ def features_bench(args, world: int, rank: int, dist, device, json_fd) -> dict:
     prof = ctx.profile_read()
     ctx.profile_reset(False)
     info = ctx.features_groupby_info()
+    if args.dump_outputs and rank == 0:
+        # the timed step keeps its counters on the device: the same step on the
+        # same resident events once more, read back
+        counts, mx = ctx.features_aggregate_resident(to_host=True)
+        dump_outputs(args.dump_outputs, {**sampled("counts", counts), "max_ts_us": [mx]})
     if dist is not None:
         import torch
 
@@ -167,7 +226,7 @@ def features_bench(args, world: int, rank: int, dist, device, json_fd) -> dict:
                      "partition_ms": prof["screen_ms"] / max(prof["steps"], 1)},
         "groupby": info,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_baseline:
         from oracle import features_oracle
 
         s_nf = 60_000
@@ -283,6 +342,11 @@ def ingest_bench(args, world: int, rank: int, dist, device, json_fd: int) -> Non
     elapsed = timed(step, args.steps)
     parse_s = timed(parse_only, args.steps) / max(args.steps, 1)
     per_step = elapsed / max(args.steps, 1)
+    if args.dump_outputs and rank == 0:
+        # the same step once more (the log bytes stay resident), read back
+        ctx.ingest_reparse()
+        counts, mx = ctx.features_aggregate_resident(to_host=True)
+        dump_outputs(args.dump_outputs, {**sampled("counts", counts), "max_ts_us": [mx]})
     nbytes = len(data)
     alg = nbytes + ne * (8 + 4 + 1 + 4 + 8)  # log read once; ends, events written
     achieved = alg / parse_s / 1e9
@@ -302,7 +366,7 @@ def ingest_bench(args, world: int, rank: int, dist, device, json_fd: int) -> Non
                      "kernel_ms": parse_s * 1e3},
         "log_GBps": nbytes / parse_s / 1e9,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_baseline:
         import tempfile
 
         s_ne = 300_000
@@ -385,7 +449,7 @@ def f64_bench(args, world: int, rank: int, dist, device, json_fd) -> dict:
         raise RuntimeError("F64 leg: the points did not load in F64 mode")
     C = X[np.sort(np.random.default_rng(42).choice(n_total, k, replace=False))].copy()
     # (the CPU baseline's sample: the first rows of the same data)
-    cpu_rows = X[:1_000_000].copy() if rank == 0 and world == 1 and not args.no_cpu_baseline else None
+    cpu_rows = X[:1_000_000].copy() if rank == 0 and world == 1 and args.cpu_baseline else None
     del X
 
     def step(C):
@@ -441,6 +505,13 @@ def f64_bench(args, world: int, rank: int, dist, device, json_fd) -> dict:
         elapsed = float(t.item())
     prof = ctx.profile_read()
     ctx.profile_reset(False)
+    if args.dump_outputs and rank == 0:
+        # the centroids after the last timed step and, on one GPU, that
+        # step's labels (of C before its update, as kmeans() returns them)
+        arrays = {"centroids": C}
+        if comm is None:
+            arrays.update(sampled("labels", ctx.labels()))
+        dump_outputs(args.dump_outputs, arrays)
     assign_ms = prof["screen_ms"] / max(prof["steps"], 1)
     kern_ms = prof["step_ms"] / max(prof["steps"], 1)
     n_local = ctx.info()["n"]
@@ -466,7 +537,7 @@ def f64_bench(args, world: int, rank: int, dist, device, json_fd) -> dict:
         "step_traffic": pmc_step_bytes("f64", n_local),
         "f64_blocks_walked": ctx.f64_walked(),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_baseline:
         from oracle import kmeans_oracle
 
         iters = 2
@@ -590,13 +661,25 @@ def main() -> None:
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                     help="strong (default): the config's n points in total over the N GPUs; "
                          "weak: n points per GPU (N x n in total)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU "
+                         "baseline, the repeated seeding and, for config 3 at N = 1, the "
+                         "other configs' legs (secondary)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned as "
+                         "DIR/<name>.npy (float64, at most 64 MiB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="config 3 at N = 1: skip the other configs' legs (secondary)")
+                    help="with --full, config 3 at N = 1: skip the other configs' legs "
+                         "(secondary)")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED)
     ap.add_argument("--rccl", action="store_true",
                     help="use torch.distributed (RCCL) even at WORLD_SIZE=1 (path testing)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)
     json_fd = os.dup(1)
@@ -636,7 +719,7 @@ def main() -> None:
             dist.destroy_process_group()
         return
     out = lloyd_bench(args, world, rank, local_rank, dist, device)
-    if world == 1 and args.config == "3" and not args.no_secondary and not args.n_total:
+    if world == 1 and args.config == "3" and args.full and not args.no_secondary and not args.n_total:
         out["secondary"] = secondary_configs(args, rank, local_rank)
     if rank == 0:
         os.write(json_fd, (json.dumps(out) + "\n").encode())
@@ -661,7 +744,7 @@ def secondary_configs(args, rank: int, local_rank: int) -> dict:
             ("f64", {"steps": 20, "warmup": 2}, f64_bench)]
     for name, over, fn in plan:
         a2 = _ap.Namespace(**vars(args))
-        a2.config, a2.n_total, a2.no_cpu_baseline = name, 0, True
+        a2.config, a2.n_total, a2.cpu_baseline, a2.dump_outputs = name, 0, False, None
         for key, v in over.items():
             setattr(a2, key, v)
         t0 = time.perf_counter()
@@ -710,14 +793,16 @@ def lloyd_bench(args, world: int, rank: int, local_rank: int, dist, device) -> d
     t0 = time.perf_counter()
     C = seed_sharded(ctx, comm, begin, n_total, k, random_state=42)
     seed_s = time.perf_counter() - t0
-    # the same seeding again with the context's buffers and seeding copies in
-    # place (the first run also allocates them and builds the fp16 copy):
-    # steady-state seeding, reported beside seed_s, never instead of it
-    t0 = time.perf_counter()
-    C2 = seed_sharded(ctx, comm, begin, n_total, k, random_state=42)
-    seed_warm_s = time.perf_counter() - t0
-    if not np.array_equal(C, C2):
-        raise RuntimeError("the second seeding run gave other centres")
+    seed_warm_s = None
+    if args.full:
+        # the same seeding again with the context's buffers and seeding copies
+        # in place (the first run also allocates them and builds the fp16
+        # copy): steady-state seeding, reported beside seed_s, never instead
+        t0 = time.perf_counter()
+        C2 = seed_sharded(ctx, comm, begin, n_total, k, random_state=42)
+        seed_warm_s = time.perf_counter() - t0
+        if not np.array_equal(C, C2):
+            raise RuntimeError("the second seeding run gave other centres")
 
     # tol disabled: exactly warmup + steps Lloyd iterations, every one of them
     # assign + fused update + all-reduce + means on the device
@@ -742,7 +827,11 @@ def lloyd_bench(args, world: int, rank: int, local_rank: int, dist, device) -> d
         raise RuntimeError(f"ran {done} of {args.steps} steps")
     prof = ctx.profile_read()
     st = run.status
-    run.finish()
+    C_last, _ = run.finish()
+    if args.dump_outputs and rank == 0:
+        # what kmeans() returns from this loop: the centroids after the last
+        # timed step and that step's labels (this rank's rows)
+        dump_outputs(args.dump_outputs, {"centroids": C_last, **sampled("labels", ctx.labels())})
     scoring_ms = None
     if args.config == "5":
         # the config's "+ replica scoring per cluster" (src/main.py:96-107,
@@ -871,7 +960,7 @@ def lloyd_bench(args, world: int, rank: int, local_rank: int, dist, device) -> d
     if scoring_ms is not None:
         out["replica_scoring_ms"] = scoring_ms
     ctx.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(d, k, args.seed)
     return out
 
