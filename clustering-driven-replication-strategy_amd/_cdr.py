@@ -92,6 +92,7 @@ SIGNATURES = {
     "cdr_f64s_finish": ([_P, _P, _P, _P, _P, _P], None),
     "cdr_f64s_chain": ([_P, _P], None),
     "cdr_profile_kernel": ([_P, _P, _I32], None),
+    "cdr_lloyd_screen_layout": ([_P, _P], None),
     "cdr_points_sqdev": ([_P, _P, _PF64], None),
     "cdr_lloyd_begin": ([_P, _P, _I32, _F64, _I32, _P, _F64], None),
     "cdr_lloyd_enqueue_assign": ([_P, _P], None),
@@ -584,6 +585,14 @@ class Context:
         buf = ctypes.create_string_buffer(96)
         _check(self._lib.cdr_profile_kernel(self._h, buf, 96))
         return buf.value.decode()
+
+    def screen_layout(self) -> dict:
+        """Work distribution of the last bounded-screen launch
+        (cdr_lloyd_screen_layout); every value 0 when none has run."""
+        out = np.zeros(6, dtype=np.int32)
+        _check(self._lib.cdr_lloyd_screen_layout(self._h, _ptr(out)))
+        names = ("workgroups", "slot_wg", "dyn_pct", "max_chunks", "nchunks", "word_bytes")
+        return {nm: int(v) for nm, v in zip(names, out)}
 
     # -- device-resident Lloyd loop (csrc/loop.hip) ---------------------------
     LL_RUNNING, LL_CONVERGED, LL_EMPTY, LL_HOST_PLAN, LL_AMBIGUOUS = 0, 1, 2, 3, 4

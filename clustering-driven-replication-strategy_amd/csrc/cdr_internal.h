@@ -101,7 +101,8 @@ constexpr int kPointGroup = 64;   // points per wave iteration in the screen
 // default path.  The switches the tests use to reach a tested alternative
 // (CDR_BOUNDS, CDR_NO_DELTA, CDR_S32B_SPLIT, CDR_S32BS_SPLIT, CDR_EXACT_ASSIGN,
 // CDR_F64_SERIAL, CDR_F64S_FORCE_CHAIN, CDR_GROUPBY_SORT, CDR_GB_BLOCK,
-// CDR_GB_BALLOT, CDR_GB_PASS3) are read with getenv in both builds.
+// CDR_GB_BALLOT, CDR_GB_PASS3, CDR_S32BS_CUS, CDR_S32BS_DYN_MIN) are read with
+// getenv in both builds.
 inline const char* exp_env(const char* name) {
 #ifdef CDR_EXPERIMENTS
   return std::getenv(name);
@@ -244,6 +245,9 @@ struct Ctx {
   DevBuf rs_hist;  // radix.hip: per-tile digit counts and digit bases of the fallback sort
   DevBuf s32_dyn;  // screen32bs16's dynamic-tail counters (2 parities x 4 regions x 8 XCDs)
   int s32_dyn_par = 0;  // the parity the next launch claims from
+  // the last bounded-screen launch (cdr_lloyd_screen_layout): workgroups,
+  // slot_wg, dyn_pct, bs_max_chunks, nchunks, word bytes; zeros: none yet
+  int32_t s32_layout[6] = {0, 0, 0, 0, 0, 0};
   DevBuf zl, zn;  // split bounded screen: per-wave lists of failed points (screen32bz), lengths
   bool zb_valid = false, xh_valid = false, bnd_ok = false;
   int zb_fmt = 0;  // bound words in zb: 16 (2-byte, screen32bs) or 32 bits

@@ -1924,6 +1924,13 @@ int cdr_profile_kernel(cdr_ctx* h, char* buf, int32_t len) {
   CDR_CATCH
 }
 
+int cdr_lloyd_screen_layout(cdr_ctx* h, int32_t out[6]) {
+  CDR_TRY
+  if (!h || !out) CDR_FAIL(CDR_ERR_ARG, "null argument");
+  for (int i = 0; i < 6; ++i) out[i] = h->c.s32_layout[i];
+  CDR_CATCH
+}
+
 // Test hook: screen values of every point (n_pad x ceil(k/16)*16 floats, host
 // buffer) from one F32X step with centroids C.  Not part of the product path.
 int cdr_debug_screen(cdr_ctx* h, const double* C, int32_t k, float* out_vals,

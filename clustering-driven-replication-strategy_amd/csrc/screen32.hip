@@ -3683,7 +3683,7 @@ static void screen32d_step(Ctx& c, int QH, int MT, int k, const h8* dfrag, const
   const int LRn = HO && QH == 2 && lr_env >= 2 && lr_env <= 4 ? lr_env : 0;
   ensure_split(c, HO ? (QH == 2 ? 3 : 4) : QH);
   const int64_t groups = c.n_pad / 64;
-  const int cus = lloyd_num_cus(c.device);
+  int cus = lloyd_num_cus(c.device);
   // pruned screen (screen32p) on the hi-only copy: CDR_PRUNE=0 turns it off
   static const bool pr_env = !exp_env("CDR_PRUNE") || std::atoi(exp_env("CDR_PRUNE"));
   const bool PR = pr_env && HO && c.prune_on;
@@ -3701,6 +3701,14 @@ static void screen32d_step(Ctx& c, int QH, int MT, int k, const h8* dfrag, const
   // screen32b with its queue and fused fixup)
   const bool BS = BND && (!std::getenv("CDR_S32B_SPLIT") || std::atoi(std::getenv("CDR_S32B_SPLIT")));
   if (!BND) c.zb_valid = false;  // another path decides this step's labels
+  // tests: screen32bs's grid sized as on a device of CDR_S32BS_CUS CUs (a
+  // multiple of 8, at most the real count; anything else is ignored), so the
+  // generation regions and the dynamic tail run at small n; read on every call
+  if (BS) {
+    const char* e = std::getenv("CDR_S32BS_CUS");
+    const int v = e ? std::atoi(e) : 0;
+    if (v >= 8 && v % 8 == 0 && v <= cus) cus = v;
+  }
   int bpc;
   const int PD = PR ? PPD : LRn ? LRn : s32d_depth(QH);
   if (BS) {
@@ -3953,8 +3961,15 @@ static void screen32d_step(Ctx& c, int QH, int MT, int k, const h8* dfrag, const
           if (const char* e = exp_env("CDR_S32BS_DYN")) dyn_env = std::atoi(e);
           dyn_env = std::min(std::max(dyn_env, 0), 100);
         }
+        // (tests: CDR_S32BS_DYN_MIN = m >= 1 in place of kS32DynMinChunks;
+        // read on every call)
+        int dyn_min = kS32DynMinChunks;
+        if (const char* e = std::getenv("CDR_S32BS_DYN_MIN")) {
+          const int v = std::atoi(e);
+          if (v >= 1) dyn_min = v;
+        }
         if (dyn_env < 100 && bs_max_region(b, nwg) < (1 << 17) && b.slot_wg % 8 == 0 &&
-            bs_max_chunks(b, nwg) >= kS32DynMinChunks) {
+            bs_max_chunks(b, nwg) >= dyn_min) {
           if (c.s32_dyn.bytes < sizeof(unsigned) * 2 * 32 * 32) {
             c.s32_dyn.ensure(sizeof(unsigned) * 2 * 32 * 32);
             HIP_CHECK(hipMemsetAsync(c.s32_dyn.p, 0, c.s32_dyn.bytes, c.stream));
@@ -3965,6 +3980,13 @@ static void screen32d_step(Ctx& c, int QH, int MT, int k, const h8* dfrag, const
           c.s32_dyn_par ^= 1;
         }
       }
+      // the launch's work distribution (cdr_lloyd_screen_layout)
+      c.s32_layout[0] = nwg;
+      c.s32_layout[1] = b.slot_wg;
+      c.s32_layout[2] = b.dyn_pct;
+      c.s32_layout[3] = (int32_t)bs_max_chunks(b, nwg);
+      c.s32_layout[4] = (int32_t)b.nchunks;
+      c.s32_layout[5] = z16 ? 2 : 4;
 #ifdef CDR_EXPERIMENTS
       static unsigned long long* tprof_buf = nullptr;
       const bool tprof_on = BS && exp_env("CDR_S32BS_TPROF");

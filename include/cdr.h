@@ -335,6 +335,12 @@ int cdr_comm_ranks(cdr_ctx* ctx, int32_t* nranks, int32_t* rank);
 /* Name of the last screen kernel launched (for the bench's roofline line);
  * NUL-terminated, truncated to len.                                          */
 int cdr_profile_kernel(cdr_ctx* ctx, char* buf, int32_t len);
+/* Work distribution of the context's last bounded-screen launch (tests):
+ * out = {workgroups, workgroups per generation region (0: one strided split),
+ * the dynamic tail's static percent (100: off), the most chunks a wave streams
+ * statically, chunks, bytes per bound word (2 or 4)}; all zeros when no
+ * bounded screen has run on the context.                                    */
+int cdr_lloyd_screen_layout(cdr_ctx* ctx, int32_t out[6]);
 /* Test hook (not product path): screen values T (n_pad, ceil(k/16)*16) fp32
  * of one F32X step and the certification constants (A0, A1).               */
 int cdr_debug_screen(cdr_ctx* ctx, const double* C, int32_t k, float* out_vals,

@@ -24,6 +24,7 @@ def test_every_declared_symbol_is_exported_and_bound():
     lib = _cdr.load_library()
     names = _declared()
     assert len(names) >= 25
+    assert "cdr_lloyd_screen_layout" in names and hasattr(_cdr.Context, "screen_layout")
     for name in names:
         assert hasattr(lib, name), name
         assert name in _cdr.SIGNATURES, f"{name} has no ctypes signature"
