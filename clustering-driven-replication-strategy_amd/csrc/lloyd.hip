@@ -1259,8 +1259,17 @@ void lloyd_step_f32x(Ctx& c, const double* C, int32_t k, int64_t* out, bool out_
     // exact assignment for every point, then fixed-point sums from labels
     launch_assign_exact<float>(c.x32.as<float>(), c.n, c.n_pad, d, c.cent64.as<double>(), k,
                                c.labels.as<int32_t>(), cus, c.stream);
+    snprintf(c.prof_kernel, sizeof(c.prof_kernel), "assign_exact_all<%d>", d);
+    // the update table of large k without screen_big (pre_ok false) takes more
+    // than the default 64 KiB of dynamic LDS; a workgroup can have 160 KiB
     const size_t lds = (size_t)len * 8;
-    if (lds > 64 * 1024) CDR_FAIL(CDR_ERR_UNSUPPORTED, "k*(d+1) too large for the update table");
+    if (lds > 160 * 1024) CDR_FAIL(CDR_ERR_UNSUPPORTED, "k*(d+1) too large for the update table");
+    static bool uattr = false;
+    if (!uattr) {
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&update_from_labels_f32x),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      uattr = true;
+    }
     int nwg = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(c.n, 256), cus * 2));
     c.partials.ensure(sizeof(long long) * (size_t)nwg * len);
     hipLaunchKernelGGL(update_from_labels_f32x, dim3(nwg), dim3(256), lds, c.stream,
