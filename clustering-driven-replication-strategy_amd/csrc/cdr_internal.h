@@ -140,11 +140,13 @@ struct Ctx {
   DevBuf xt32;
   DevBuf muf;  // int64[d]: mu_f 2^S (screen32 restores x sums from xt sums)
   bool pre_ok = false, xt_valid = false;
-  // split screen copy for the DELTA steps (screen32d): fp16 hi / lo of
-  // xhat = fma(x, 2^sigma, -mu 2^sigma), tiled [n_pad/32][2 halves][32][16 QH B]
+  // hi-only screen copy for the DELTA steps (screen32p, screen32b): fp16 of
+  // xhat = fma(x, 2^sigma, -mu 2^sigma), tiled [n_pad/32][2 halves][32][8 QH B]
   // (the MFMA B operands as loaded); built once per point set
   DevBuf xs16;
-  DevBuf xa32;  // the points row-major (float [n_pad][d4]) for fixup32's gathers
+  // the points row-major (float [n_pad][d4]): the gathers of the fused fixup,
+  // of screen32bs, of the large-k path and of the seeding
+  DevBuf xa32;
   // large-k screen copy (screen_big_sp): fp16 of the pre-centred points as the
   // MFMA B fragments are loaded, [n_pad/64][2 tiles][DQ chunks][64 lanes] x 16 B
   DevBuf xb16;
@@ -156,9 +158,8 @@ struct Ctx {
   DevBuf big_chunks;  // L2 chunk numbering of L1's regions (big_chunk_prefix)
   bool big_valid = false;
   int big_k = 0;
-  bool xs_valid = false;
-  int xs_qh = 0;
-  DevBuf mv_list;   // screen32d: per-wave regions of moved points {pt, old | new << 16}
+  bool xs_valid = false;  // xs16 built (ensure_split)
+  DevBuf mv_list;   // screen32p / screen32b: per-wave regions of moved points {pt, old | new << 16}
   DevBuf mv_count;  // int32 per wave
 
   // ---- Lloyd ----
@@ -227,15 +228,12 @@ struct Ctx {
   // belong to the labels in `labels` (valid after a screen32 step with run_k)
   DevBuf run_sums;
   bool run_valid = false;
-  // screen32d's one-byte copy of `labels` (k <= 64): the DELTA screen reads a
-  // point's previous label from it (1 B instead of 4 B per point and step);
-  // valid while only screen32d / fixup32 wrote the labels since it was built
+  // one-byte copy of `labels` (k <= 64): the DELTA screens read a point's
+  // previous label from it (1 B instead of 4 B per point and step); valid
+  // while only DELTA steps (screen32_delta_step) wrote the labels since it
+  // was built
   DevBuf lab8;
   bool lab8_valid = false;
-  // DELTA steps on the pruned screen (screen32p, triangle-inequality
-  // certificates) instead of the k-way MFMA screen; switched off when too
-  // many points of a step stay uncertified (clusters not separated)
-  bool prune_on = true;
   // bounded DELTA steps (screen32b, device loop only): per-point bound words
   // (valid while every step since the last reset was a screen32b step whose
   // centroid move ll_finalize32 accounted in bnd), the row-major hi copy the

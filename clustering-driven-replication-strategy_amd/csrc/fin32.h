@@ -53,7 +53,7 @@ struct FinArgs {
   // tables (plan32.h kBnd*)
   long long* bnd;
   // a rebase of the 2-byte words may be decided at this step (the host then
-  // runs zh_rebase_kernel before the next screen; screen32.hip)
+  // runs zh_rebase_kernel before the next screen; screen32b.hip)
   int rebase_ok;
   int abl;  // timing experiments only (0 in the product build)
   unsigned long long* tprof;  // (experiments build: phase timestamps, thread 0)

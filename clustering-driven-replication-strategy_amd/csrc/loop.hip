@@ -42,7 +42,7 @@ bool screen32_step(Ctx& c, const double* C, int k, long long* dout, long long* h
                    float* dbg, float* thr_out, long long* gate);
 void plan32_point_side(const Ctx& c, double& xxmax, double& l1x);
 void lloyd_step_f32x(Ctx& c, const double* C, int32_t k, int64_t* out, bool out_dev);
-void zh_rebase(Ctx& c, const long long* gate);  // screen32.hip
+void zh_rebase(Ctx& c, const long long* gate);  // screen32b.hip
 constexpr int kRebaseEvery = 4;  // finalizes between 2-byte rebase opportunities
 
 constexpr int kFinThreads = 512;

@@ -234,7 +234,7 @@ def test_incremental_update_equals_full_recompute(ctx, n, d, k, monkeypatch):
 
 @pytest.mark.parametrize("d", [16, 11, 8, 5])
 def test_hi_only_screen_near_ties(ctx, d):
-    """The DELTA steps screen fp16(xhat) alone (screen32h, screen32h1): points put
+    """The DELTA steps screen fp16(xhat) alone (screen32p's drains): points put
     on the bisectors of centroid pairs and a few fp16 ulps off them must still
     get the reference's label (the per-point certificate sends them to the
     exact fallback)."""

@@ -188,7 +188,7 @@ def test_config3_every_label_exact(ctx, monkeypatch):
     equal the exact fp64 NumPy-order assignment of the same centroids
     (assign_exact_all on every point, CDR_EXACT_ASSIGN), and so do the int64
     sums; a host-plan DELTA step (pruned screen32p + queued k-way MFMA screen
-    + fixup32) on the same centroids agrees."""
+    + fused fixup) on the same centroids agrees."""
     n, d, k = 100_000_000, 16, 64
     C_prev, lab = _every_label_exact(ctx, monkeypatch, n, d, k, 25)
     ctx.lloyd_step(C_prev)

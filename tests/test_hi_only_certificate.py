@@ -1,5 +1,6 @@
-"""CPU check of the hi-only screen's certificate (csrc/screen32.hip, screen32d
-HO) in exact-enough fp64 arithmetic.
+"""CPU check of the hi-only screen's certificate (derived at the top of
+csrc/screen32_fix.h, used by the drains of screen32p and screen32b; DESIGN.md
+4.3c) in exact-enough fp64 arithmetic.
 
 The kernel screens h = fp16(xhat) instead of xhat and certifies a point when
     v_s > v_b (1 + 2^-16) + thr0 + 2 dn (sqrt(G_s) + sqrt(G_b)),

@@ -1,5 +1,8 @@
-"""In-process A/B timing of the screen kernel with parts switched off
-(interleaved rounds, HIP-event timings).  Diagnostic tool, not a test.
+"""In-process A/B timing of the general screen (screen_kernel / screen_fast in
+csrc/lloyd.hip: the shapes outside screen32 and screen_big, by default
+d = 24, k = 33) with parts switched off through cdr_debug_screen_ablate
+(interleaved rounds, HIP-event timings).  The small-shape screens
+(csrc/screen32*.hip) have no ablation arms.  Diagnostic tool, not a test.
 Needs the experiments build:  make -C .../csrc OUT=../libcdr_exp.so
 OBJDIR=../build_exp EXTRA=-DCDR_EXPERIMENTS  and  CDR_LIB=<that .so>."""
 import os
@@ -12,9 +15,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(REPO, "clustering-driven-replication-strategy_amd"), REPO]
 import _cdr  # noqa: E402
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 100_000_000
-d = int(sys.argv[2]) if len(sys.argv) > 2 else 16
-k = int(sys.argv[3]) if len(sys.argv) > 3 else 64
+n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
+d = int(sys.argv[2]) if len(sys.argv) > 2 else 24
+k = int(sys.argv[3]) if len(sys.argv) > 3 else 33
 masks = [int(m) for m in (sys.argv[4].split(",") if len(sys.argv) > 4 else "0,1,2,3,4,8,15".split(","))]
 ctx = _cdr.Context(0)
 ctx.generate_points(n, 0, n, d, k, 0x5EED)
