@@ -133,6 +133,9 @@ SIGNATURES = {
     "cdr_ingest_manifest": ([_P, _I64, _P, _P, _P, _I32, _P, _P], None),
     "cdr_ingest_log": ([_P, _P, _I64, _P], None),
     "cdr_ingest_reparse": ([_P, _P], None),
+    "cdr_quality_silhouette": ([_P, _P, _I64, _P, _I32, _P, _P, _P], None),
+    "cdr_quality_scatter": ([_P, _P, _I32, _P, _P, _P], None),
+    "cdr_quality_timing": ([_P, _P], None),
     "cdr_host_seq_sum": ([_P, _I64, _F64], ctypes.c_double),
 }
 
@@ -717,6 +720,56 @@ class Context:
         out = np.empty((self._med_k, self.info()["d"]), dtype=np.float64)
         _check(self._lib.cdr_medians_finish(self._h, _ptr(out)))
         return out
+
+    # -- cluster quality (csrc/quality.hip) -------------------------------
+    def silhouette(self, k: int, idx=None, labels=None):
+        """Silhouette of the local rows idx (None: all) with labels (None: the
+        last assignment's) in [0, k) (cdr_quality_silhouette).  Returns
+        (s (m,) in the caller's row order, per-cluster sums of s (k,),
+        per-cluster counts (k,))."""
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int64).ravel()
+        m = idx.size if idx is not None else self.info()["n"]
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+            if labels.size != m:
+                raise ValueError("labels must have one entry per sample row")
+        k = int(k)
+        s = np.empty(max(m, 1), dtype=np.float64)
+        csum = np.zeros(max(k, 1), dtype=np.float64)
+        ccnt = np.zeros(max(k, 1), dtype=np.int64)
+        _check(self._lib.cdr_quality_silhouette(
+            self._h, _ptr(idx) if idx is not None and m else None, m,
+            _ptr(labels) if labels is not None and m else None, k, _ptr(s), _ptr(csum),
+            _ptr(ccnt)))
+        return s[:m], csum[:k], ccnt[:k]
+
+    def quality_scatter(self, C: np.ndarray, labels=None):
+        """Per-cluster sums of the distances of all rows to their own centroid
+        of C (k, d) and the cluster sizes (cdr_quality_scatter); labels None:
+        the last assignment's."""
+        C = np.ascontiguousarray(C, dtype=np.float64)
+        info = self.info()
+        if C.ndim != 2 or (info["n"] and C.shape[1] != info["d"]):
+            raise ValueError("centroids must be (k, d) with the points' d")
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+            if labels.size != info["n"]:
+                raise ValueError("labels must have one entry per resident row")
+        k = C.shape[0]
+        sums = np.zeros(max(k, 1), dtype=np.float64)
+        counts = np.zeros(max(k, 1), dtype=np.int64)
+        _check(self._lib.cdr_quality_scatter(
+            self._h, _ptr(C), k, _ptr(labels) if labels is not None and labels.size else None,
+            _ptr(sums), _ptr(counts)))
+        return sums[:k], counts[:k]
+
+    def quality_timing(self) -> dict:
+        """Kernel times of the last quality calls (cdr_quality_timing)."""
+        out = np.zeros(4, dtype=np.float64)
+        _check(self._lib.cdr_quality_timing(self._h, _ptr(out)))
+        return {"pairs_ms": out[0], "pairs_max_launch_ms": out[1], "pair_launches": int(out[2]),
+                "scatter_ms": out[3]}
 
     # -- features --------------------------------------------------------
     def features_aggregate(self, file_idx, op, client, ts_us, primary):

@@ -101,7 +101,7 @@ constexpr int kPointGroup = 64;   // points per wave iteration in the screen
 // default path.  The switches the tests use to reach a tested alternative
 // (CDR_BOUNDS, CDR_NO_DELTA, CDR_S32B_SPLIT, CDR_S32BS_SPLIT, CDR_EXACT_ASSIGN,
 // CDR_F64_SERIAL, CDR_F64S_FORCE_CHAIN, CDR_GROUPBY_SORT, CDR_GB_BLOCK,
-// CDR_GB_BALLOT, CDR_GB_PASS3, CDR_S32BS_CUS, CDR_S32BS_DYN_MIN) are read with
+// CDR_GB_BALLOT, CDR_GB_PASS3, CDR_S32BS_CUS, CDR_S32BS_DYN_MIN, CDR_QUALITY_BUDGET) are read with
 // getenv in both builds.
 inline const char* exp_env(const char* name) {
 #ifdef CDR_EXPERIMENTS
@@ -315,6 +315,11 @@ struct Ctx {
 
   // ---- medians / features scratch ----
   DevBuf med_vals, med_off, med_out, med_tmp, med_tmp2, med_hist;
+  // quality.hip: one scratch allocation (carved per call), and the kernel times
+  // of the last calls {pair kernels ms, longest pair launch ms, pair launches,
+  // scatter kernels ms} (cdr_quality_timing)
+  DevBuf q_buf;
+  double q_ms[4] = {0.0, 0.0, 0.0, 0.0};
   int32_t med_k = 0;  // clusters of the grouped rows (cdr_medians_group)
   // timestamp range of the resident events (min, max, any null), computed by
   // the producer that wrote them (events_ts_range, groupby.hip); valid for

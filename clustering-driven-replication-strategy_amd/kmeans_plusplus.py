@@ -178,9 +178,15 @@ def kmeans(X, k, number_of_files=100, tol=1e-4, random_state=None, *,
     (int64) from the last assignment — exactly as the reference does.
     """
     X = np.asarray(X)
-    n_samples = X.shape[0]
     ctx = context if context is not None else default_context()
     ctx.load_points(X)
+    return _kmeans_loaded(ctx, X, k, number_of_files, tol, random_state, max_iter)
+
+
+def _kmeans_loaded(ctx: Context, X: np.ndarray, k, number_of_files, tol, random_state, max_iter):
+    """kmeans() on points already resident in `ctx` (X is their host copy):
+    cluster_quality.sweep runs several k on one load."""
+    n_samples = X.shape[0]
     centroids = _seed(ctx, X, k, random_state)
 
     if max_iter is None:

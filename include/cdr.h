@@ -484,6 +484,37 @@ int cdr_features_finalize(cdr_ctx* ctx, int64_t n_files, const int64_t* counts,
                           const double* creation_s, double observation_end,
                           double* out);
 
+/* ---- cluster quality (extension: no reference counterpart) ------------- */
+/* Validity indices of a clustering of the resident points, for choosing the
+ * k the reference fixes (src/main.py --k).  The distance is the reference's
+ * np.linalg.norm(x - y) (src/kmeans_plusplus.py:33): sqrt(sum_f (x_f - y_f)^2)
+ * in fp64 on the float64 values of the points, in either storage mode.  No
+ * floating-point atomics: the same input gives bit-identical output.
+ *
+ * cdr_quality_silhouette: silhouette of the m local rows idx (NULL: all rows,
+ *   m == n) with labels in [0, k) (NULL: the labels of the last assignment).
+ *   With c_A the rows of the sample labelled A, for row i of cluster A:
+ *   a_i = sum_{j in A, j != i} d(i, j) / (c_A - 1), b_i = min over B != A with
+ *   c_B > 0 of sum_{j in B} d(i, j) / c_B, s_i = (b_i - a_i) / max(a_i, b_i)
+ *   (0 when a_i = b_i = 0 or c_A == 1).  s (m) in the caller's row order;
+ *   cluster_sum[j] = sum of s_i over cluster j, cluster_count[j] = c_j (either
+ *   may be NULL).  1 <= d <= 64 and k <= 1024, else CDR_ERR_UNSUPPORTED;
+ *   CDR_ERR_ARG for m outside [2, 2^20], a row or label out of range, or a
+ *   number of non-empty clusters outside [2, m - 1]; CDR_ERR_STATE without
+ *   points, or without labels on the device when labels == NULL.
+ * cdr_quality_scatter: the device part of Davies-Bouldin over all n rows:
+ *   sums[j] = sum over the rows labelled j of d(x, C_j) for centroids C (k, d),
+ *   counts[j] = their number; labels NULL (resident) or n values.  Same
+ *   shapes and errors.  (S_j = sums / counts; the k x k part is host work.)
+ * cdr_quality_timing: out[4] = kernel times of the last calls {silhouette pair
+ *   kernels ms (sum), the longest single pair launch ms, pair launches,
+ *   scatter kernels ms}.                                                     */
+int cdr_quality_silhouette(cdr_ctx* ctx, const int64_t* idx, int64_t m, const int64_t* labels,
+                           int32_t k, double* s, double* cluster_sum, int64_t* cluster_count);
+int cdr_quality_scatter(cdr_ctx* ctx, const double* C, int32_t k, const int64_t* labels,
+                        double* sums, int64_t* counts);
+int cdr_quality_timing(cdr_ctx* ctx, double* out);
+
 /* ---- host helpers (plain C on the host, no device) --------------------- */
 /* ((init + v[0]) + v[1]) + ... in fp64, left to right.                      */
 double cdr_host_seq_sum(const double* v, int64_t n, double init);
