@@ -181,7 +181,10 @@ class Comm:
         """Element-wise SUM / MIN / MAX of an int64 vector over the ranks."""
         if not self.dist:
             return np.asarray(arr, dtype=np.int64)
-        t = self._t(np.asarray(arr, dtype=np.int64))
+        # a copy: on a host communicator the tensor shares the array's memory and
+        # the reduction would overwrite the caller's input (ensure_unified reduces
+        # one vector twice, MIN then MAX)
+        t = self._t(np.array(arr, dtype=np.int64))
         red = {"sum": self.dist.ReduceOp.SUM, "min": self.dist.ReduceOp.MIN,
                "max": self.dist.ReduceOp.MAX}[op]
         self.dist.all_reduce(t, op=red)
@@ -190,7 +193,7 @@ class Comm:
     def allreduce_f64(self, arr: np.ndarray, op: str = "sum") -> np.ndarray:
         if not self.dist:
             return np.asarray(arr, dtype=np.float64)
-        t = self._t(np.asarray(arr, dtype=np.float64))
+        t = self._t(np.array(arr, dtype=np.float64))  # a copy, as in allreduce_i64
         red = {"sum": self.dist.ReduceOp.SUM, "min": self.dist.ReduceOp.MIN,
                "max": self.dist.ReduceOp.MAX}[op]
         self.dist.all_reduce(t, op=red)
@@ -771,6 +774,18 @@ def sharded_medians(ctx, comm: Comm, k: int) -> np.ndarray:
     (k, d) array, equal to the single-process medians."""
     if comm.world == 1:
         return ctx.medians_by_label(k)  # the same passes, histograms never leave the device
+    # The storage mode sets the key width and the number of passes (4 for
+    # F32X, 8 for F64): ranks that disagree would issue different numbers of
+    # all-reduces over different key spaces, so they all raise here instead.
+    # (A context without info(), the NumPy stand-in of the tests, is skipped,
+    # as in ensure_unified.)
+    if hasattr(ctx, "info"):
+        mode = np.array([ctx.info()["mode"]], dtype=np.int64)
+        lo, hi = comm.allreduce_i64(mode, "min"), comm.allreduce_i64(mode, "max")
+        if int(lo[0]) != int(hi[0]):
+            raise RuntimeError("sharded_medians: the ranks' points are stored in different modes "
+                               f"(min {int(lo[0])}, max {int(hi[0])}); bring them to one with "
+                               "cdr_dist.unify_points before the Lloyd step")
     local = ctx.medians_group(k)
     counts = comm.allreduce_i64(local, "sum")
     passes, words = ctx.medians_begin(counts)

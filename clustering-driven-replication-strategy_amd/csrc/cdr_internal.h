@@ -320,7 +320,12 @@ struct Ctx {
   // scatter kernels ms} (cdr_quality_timing)
   DevBuf q_buf;
   double q_ms[4] = {0.0, 0.0, 0.0, 0.0};
-  int32_t med_k = 0;  // clusters of the grouped rows (cdr_medians_group)
+  // clusters of the grouped rows (cdr_medians_group); 0 = none: whatever
+  // replaces the points, rewrites the labels or reuses med_vals / med_off /
+  // med_out (medians_segmented) clears it, and the pass entries refuse to run.
+  // med_begun: cdr_medians_begin has sized and filled med_out for this grouping
+  int32_t med_k = 0;
+  bool med_begun = false;
   // timestamp range of the resident events (min, max, any null), computed by
   // the producer that wrote them (events_ts_range, groupby.hip); valid for
   // ev_tsr_n events until another writer of ev_ts clears ev_tsr_valid

@@ -298,6 +298,7 @@ static void decide_mode(Ctx& c, const std::vector<unsigned long long>& st,
     c.x64.release();
   }
   c.have_labels = false;
+  c.med_k = 0;  // (load, generate and restat all end here) the grouped rows are of other points
   c.run_valid = false;
   c.lab8_valid = false;
   c.zb_valid = false;
@@ -331,6 +332,7 @@ static void reset_points(Ctx& c, int64_t n, int32_t d) {
   c.lab8_valid = false;
   c.zb_valid = false;
   c.ll_on = false;
+  c.med_k = 0;
   c.labels.ensure(sizeof(int32_t) * c.n_pad);
   HIP_CHECK(hipMemsetAsync(c.labels.p, 0, sizeof(int32_t) * c.n_pad, c.stream));
 }

@@ -1296,6 +1296,7 @@ void lloyd_step_f32x(Ctx& c, const double* C, int32_t k, int64_t* out, bool out_
   }
   c.last_k = k;
   c.have_labels = true;
+  c.med_k = 0;  // new labels: the grouped rows (medians.hip) are stale
   if (!out_dev) {
     int32_t fb = 0;
     if (s32) {
@@ -1453,6 +1454,7 @@ void lloyd_run_f64(Ctx& c, const double* C, int32_t k, int32_t max_steps, double
   info[1] = max_steps == 0 ? 0 : (int32_t)hst[2];
   c.last_k = k;
   c.have_labels = max_steps > 0 || c.have_labels;
+  c.med_k = 0;  // new labels: the grouped rows (medians.hip) are stale
   c.last_fallback = c.n;
 }
 
@@ -1492,6 +1494,7 @@ void lloyd_step_f64(Ctx& c, const double* C, int32_t k, double* sums, int64_t* c
       for (long long v : w) c.f64x_walked += v;
       c.last_k = k;
       c.have_labels = true;
+      c.med_k = 0;  // new labels: the grouped rows (medians.hip) are stale
       c.last_fallback = c.n;
       return;
     }
@@ -1534,6 +1537,7 @@ void lloyd_step_f64(Ctx& c, const double* C, int32_t k, double* sums, int64_t* c
   HIP_CHECK(hipStreamSynchronize(c.stream));
   c.last_k = k;
   c.have_labels = true;
+  c.med_k = 0;  // new labels: the grouped rows (medians.hip) are stale
   c.last_fallback = c.n;
 }
 
@@ -1677,6 +1681,7 @@ void lloyd_step_f32r(Ctx& c, const float* C, int32_t k, double* sums, int64_t* c
   HIP_CHECK(hipStreamSynchronize(c.stream));
   c.last_k = k;
   c.have_labels = true;
+  c.med_k = 0;  // new labels: the grouped rows (medians.hip) are stale
   c.last_fallback = c.n;
 }
 
@@ -1751,6 +1756,7 @@ int cdr_f64s_begin(cdr_ctx* h, const double* C, int32_t k, int32_t nranks, int32
   sizes[1] = (int64_t)24 * kd * (f64s_cap() + 1);
   c.last_k = k;
   c.have_labels = true;
+  c.med_k = 0;  // new labels: the grouped rows (medians.hip) are stale
   CDR_CATCH
 }
 

@@ -412,6 +412,7 @@ static void ll_enqueue_assign(Ctx& c, int64_t* dsums) {
       lloyd_step_f32x(c, Ch.data(), c.ll_k, reinterpret_cast<int64_t*>(dout), true);
     }
   }
+  c.med_k = 0;  // new labels: the grouped rows (medians.hip) are stale
   c.ll_enqueued += 1;
 }
 

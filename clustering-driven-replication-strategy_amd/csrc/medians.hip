@@ -391,6 +391,7 @@ void medians_segmented(Ctx& c, const double* values, const int64_t* offsets, int
   if (total < 0) CDR_FAIL(CDR_ERR_ARG, "offsets must be non-decreasing");
   for (int64_t s = 0; s < nseg; ++s)
     if (offsets[s + 1] < offsets[s]) CDR_FAIL(CDR_ERR_ARG, "offsets must be non-decreasing");
+  c.med_k = 0;  // the grouped rows of cdr_medians_group live in these buffers
   c.med_vals.ensure(sizeof(double) * (total > 0 ? total : 1));
   c.med_off.ensure(sizeof(int64_t) * (nseg + 1));
   c.med_out.ensure(sizeof(double) * nseg);
@@ -413,10 +414,24 @@ void medians_segmented(Ctx& c, const double* values, const int64_t* offsets, int
 // ---- host side of the label medians (single shard or one rank of several) --
 static int mg_passes(const Ctx& c) { return c.mode == CDR_MODE_F32X ? 4 : 8; }
 
+// The grouped state (med_k, med_vals, med_off, and med_out once begun) is
+// valid only for the points, labels and buffers it was built from; whoever
+// changes one of them clears med_k.
+static void mg_need_group(const Ctx& c, bool begun) {
+  if (c.med_k <= 0)
+    CDR_FAIL(CDR_ERR_STATE,
+             "medians: no grouped rows of the current points and labels: call "
+             "cdr_medians_group first");
+  if (begun && !c.med_begun)
+    CDR_FAIL(CDR_ERR_STATE, "medians: call cdr_medians_begin after cdr_medians_group");
+}
+
 void medians_group(Ctx& c, int32_t k, int64_t* counts) {
   if (!c.have_labels) CDR_FAIL(CDR_ERR_STATE, "no Lloyd labels: run cdr_lloyd_step first");
   if (k < 1 || k < c.last_k) CDR_FAIL(CDR_ERR_ARG, "k smaller than the labels' k");
   if (k > kMgMaxK) CDR_FAIL(CDR_ERR_UNSUPPORTED, "medians: k > 8192");
+  c.med_k = 0;
+  c.med_begun = false;
   const int d = c.d;
   const int64_t n = c.n;
   if (n >= (1ll << 32)) CDR_FAIL(CDR_ERR_UNSUPPORTED, "medians: 2^32 points or more per shard");
@@ -459,8 +474,8 @@ void medians_group(Ctx& c, int32_t k, int64_t* counts) {
 }
 
 int medians_begin(Ctx& c, const int64_t* global_counts) {
+  mg_need_group(c, false);
   const int k = c.med_k, d = c.d;
-  if (k <= 0) CDR_FAIL(CDR_ERR_STATE, "medians: group the rows first (cdr_medians_group)");
   for (int j = 0; j < k; ++j)
     if (global_counts[j] >= (1ll << 32))
       CDR_FAIL(CDR_ERR_UNSUPPORTED, "medians: a cluster of 2^32 points or more");
@@ -476,12 +491,14 @@ int medians_begin(Ctx& c, const int64_t* global_counts) {
                      k, pref, rank);
   HIP_CHECK(hipGetLastError());
   c.med_hist.ensure(sizeof(unsigned) * 512 * kd);
+  c.med_begun = true;
   return mg_passes(c);
 }
 
 // hist: where the pass's histograms go ([k][d][2][256] u32; host or device
 // memory; nullptr = leave them in the context for the select step)
 void medians_pass_hist(Ctx& c, int pass, void* hist) {
+  mg_need_group(c, true);
   const int k = c.med_k, d = c.d, P = mg_passes(c);
   if (pass < 0 || pass >= P) CDR_FAIL(CDR_ERR_ARG, "medians: pass out of range");
   const size_t kd = (size_t)k * d;
@@ -506,6 +523,7 @@ void medians_pass_hist(Ctx& c, int pass, void* hist) {
 }
 
 void medians_pass_select(Ctx& c, int pass, const void* hist) {
+  mg_need_group(c, true);
   const int k = c.med_k, d = c.d, P = mg_passes(c);
   if (pass < 0 || pass >= P) CDR_FAIL(CDR_ERR_ARG, "medians: pass out of range");
   const size_t kd = (size_t)k * d;
@@ -526,6 +544,7 @@ void medians_pass_select(Ctx& c, int pass, const void* hist) {
 }
 
 void medians_finish(Ctx& c, double* out) {
+  mg_need_group(c, true);
   const int k = c.med_k, d = c.d;
   const size_t kd = (size_t)k * d;
   long long* gcnt = c.med_out.as<long long>();

@@ -363,7 +363,13 @@ int cdr_medians_by_label(cdr_ctx* ctx, int32_t k, double* out);
  * per pass, cdr_medians_pass_hist writes this shard's digit histograms to
  * `hist` (host or device memory), the caller SUM-all-reduces them, and
  * cdr_medians_pass_select consumes the global histograms; cdr_medians_finish
- * writes out (k, d).  Every rank gets the medians of the whole data set.    */
+ * writes out (k, d).  Every rank gets the medians of the whole data set.
+ * The grouped rows are valid only for the points, labels and buffers they
+ * were built from: loading, generating or restat'ing points, any Lloyd step
+ * (it rewrites the labels) and cdr_medians_segmented (it reuses the buffers)
+ * discard them, and cdr_medians_begin / _pass_hist / _pass_select / _finish
+ * then fail with CDR_ERR_STATE until cdr_medians_group has run again (the
+ * pass entries and _finish also until cdr_medians_begin has).               */
 int cdr_medians_group(cdr_ctx* ctx, int32_t k, int64_t* counts);
 int cdr_medians_begin(cdr_ctx* ctx, const int64_t* global_counts, int32_t* passes,
                       int64_t* hist_words);

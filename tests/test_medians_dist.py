@@ -139,3 +139,108 @@ def test_sharded_medians_equal_numpy(tmp_path, world):
         got = [np.load(tmp_path / f"m{r}.npy") for r in range(world)]
     for g in got:
         np.testing.assert_array_equal(g, exp)
+
+
+class _ModeMedians(NumpyMedians):
+    """The stand-in with a storage mode to report (info() as _cdr.Context's)."""
+
+    def __init__(self, X, labels, mode):
+        super().__init__(X, labels)
+        self._mode = mode
+
+    def info(self):
+        return {"n": self.X.shape[0], "d": self.X.shape[1], "mode": self._mode, "scale_bits": 0}
+
+
+def _mode_worker(rank, world, port, out_dir):
+    import torch.distributed as dist
+
+    from cdr_dist import Comm, sharded_medians
+
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    X, lab = _data()
+    lo, hi = (X.shape[0] * rank) // world, (X.shape[0] * (rank + 1)) // world
+    # rank 0 reports F32X (mode 1), rank 1 F64 (mode 2); the stand-in always
+    # does 8 passes, so a library without the check returns instead of hanging
+    msg = "returned"
+    try:
+        sharded_medians(_ModeMedians(X[lo:hi], lab[lo:hi], 1 + rank), Comm(dist, None), 6)
+    except RuntimeError as e:
+        msg = "RuntimeError: %s" % e
+    with open(os.path.join(out_dir, f"mode{rank}.txt"), "w") as fh:
+        fh.write(msg)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_sharded_medians_refuse_mixed_modes(tmp_path):
+    """One rank F32X, the other F64: both raise together before the first
+    pass (neither is left waiting in a collective) and name unify_points."""
+    mp = pytest.importorskip("torch.multiprocessing")
+    mp.spawn(_mode_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    for r in range(2):
+        msg = (tmp_path / f"mode{r}.txt").read_text()
+        assert msg.startswith("RuntimeError"), (r, msg)
+        assert "unify_points" in msg, (r, msg)
+
+
+def test_sharded_medians_same_mode_with_info(tmp_path):
+    """The check itself changes nothing when the ranks agree."""
+    from cdr_dist import Comm, sharded_medians
+
+    X, lab = _data()
+    got = sharded_medians(_ModeMedians(X, lab, 2), Comm(None), 6)
+    np.testing.assert_array_equal(got, _exp(X, lab, 6))
+
+
+class _UnifiedStub:
+    """What ensure_unified needs of a context already restat'ed over n_total
+    rows, with a storage mode per rank."""
+
+    def __init__(self, mode, n_total):
+        self._mode, self.restat_n = mode, n_total
+
+    def points_restat(self, st, n_sum):  # pragma: no cover - restat_n says it is not needed
+        raise AssertionError("already unified")
+
+    def info(self):
+        return {"n": 10, "d": 3, "mode": self._mode, "scale_bits": 0}
+
+
+def _reduce_worker(rank, world, port, out_dir):
+    import torch.distributed as dist
+
+    from cdr_dist import Comm, ensure_unified
+
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    comm = Comm(dist, None)
+    v = np.array([1 + rank, 10 - rank], dtype=np.int64)
+    keep = v.copy()
+    lo, hi = comm.allreduce_i64(v, "min"), comm.allreduce_i64(v, "max")
+    f = np.array([0.5 + rank])
+    fsum = comm.allreduce_f64(f, "sum")
+    ok = (np.array_equal(v, keep) and lo.tolist() == [1, 9] and hi.tolist() == [2, 10]
+          and f[0] == 0.5 + rank and fsum[0] == 2.0)
+    msg = "returned"
+    try:
+        ensure_unified(_UnifiedStub(1 + rank, 20), comm, 20)
+    except RuntimeError as e:
+        msg = "RuntimeError: %s" % e
+    with open(os.path.join(out_dir, f"red{rank}.txt"), "w") as fh:
+        fh.write("%s|%s" % (ok, msg))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_host_allreduce_keeps_its_input_and_ensure_unified_sees_modes(tmp_path):
+    """On a host (gloo) communicator the reduced tensor shared the caller's
+    array: a MIN followed by a MAX of the same vector compared the minimum
+    with itself, so ensure_unified never saw ranks that disagree."""
+    mp = pytest.importorskip("torch.multiprocessing")
+    mp.spawn(_reduce_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    for r in range(2):
+        ok, msg = (tmp_path / f"red{r}.txt").read_text().split("|", 1)
+        assert ok == "True", r
+        assert msg.startswith("RuntimeError") and "storage mode" in msg, (r, msg)
