@@ -84,6 +84,7 @@ SIGNATURES = {
     "cdr_lloyd_labels": ([_P, _P], None),
     "cdr_lloyd_stats": ([_P, _PI64], None),
     "cdr_debug_screen": ([_P, _P, _I32, _P, _P], None),
+    "cdr_debug_plan32": ([_P, _I32, _P, _I32, _P], None),
     "cdr_profile_reset": ([_P, _I32], None),
     "cdr_profile_read": ([_P, _P], None),
     "cdr_profile_read_sub": ([_P, _P], None),
@@ -675,6 +676,15 @@ class Context:
         thr = np.empty(2, dtype=np.float32)
         _check(self._lib.cdr_debug_screen(self._h, _ptr(C), k, _ptr(vals), _ptr(thr)))
         return vals[: inf["n"], :k], thr
+
+    def debug_plan32(self, which: int, C: np.ndarray | None, k: int) -> np.ndarray:
+        """The screen32 plan's prune block (cdr_debug_plan32) as 1408 floats."""
+        out = np.empty(64 * 20 + 128, dtype=np.float32)
+        if C is not None:
+            C = np.ascontiguousarray(C, dtype=np.float64)
+        _check(self._lib.cdr_debug_plan32(self._h, int(which), _ptr(C) if C is not None else None,
+                                          int(k), _ptr(out)))
+        return out
 
     # -- medians ---------------------------------------------------------
     def medians_segmented(self, values: np.ndarray, offsets: np.ndarray) -> np.ndarray:

@@ -415,6 +415,7 @@ __device__ __forceinline__ void fin32_body(const FinArgs& a, unsigned char* __re
   FIN_TP(5);
   // ---- row sums (host order), nearest-centroid distances, maxima ----
   double ec[V], sm[V];
+  plan_key nk[V][3];  // the three nearest other centroids' keys (plan32.h)
 #pragma unroll
   for (int v = 0; v < V; ++v) {
     const int jj = j[v];
@@ -433,6 +434,7 @@ __device__ __forceinline__ void fin32_body(const FinArgs& a, unsigned char* __re
     }
     ec[v] = plan32_prune_ec(e2, s);
     double smv = INFINITY;  // smallest squared distance of c32_j to another c32
+    plan_key t3[3] = {kPlanNoKey, kPlanNoKey, kPlanNoKey};
     if (row[v] && !(a.abl & 4)) {
       // own row in registers, four partial sums per pair (a short dependency
       // chain; every term >= 0 and at most 6 roundings on any path, within
@@ -448,7 +450,9 @@ __device__ __forceinline__ void fin32_body(const FinArgs& a, unsigned char* __re
           const double df = (double)cj[f] - (double)c32[q * 16 + f];  // exact
           acc[f & 3] += df * df;
         }
-        smv = fmin(smv, (acc[0] + acc[1]) + (acc[2] + acc[3]));
+        const double s2 = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+        smv = fmin(smv, s2);
+        plan32_top3(t3, plan32_key(s2, q));
       }
     }
     if (v == 0) FIN_TP(6);
@@ -456,6 +460,16 @@ __device__ __forceinline__ void fin32_body(const FinArgs& a, unsigned char* __re
     smv = fmin(smv, __shfl_xor(smv, 2));
     smv = fmin(smv, __shfl_xor(smv, 4));
     sm[v] = smv;
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) {  // the row's 8 lanes' lists merged
+      plan_key u3[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) u3[i] = __shfl_xor(t3[i], o);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) plan32_top3(t3, u3[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) nk[v][i] = t3[i];
     double ccmax = head ? s : 0.0, l1c = head ? l1 : 0.0, cabs = head ? ca : 0.0,
            ecmax = head ? ec[v] : 0.0;
 #pragma unroll
@@ -502,6 +516,8 @@ __device__ __forceinline__ void fin32_body(const FinArgs& a, unsigned char* __re
     if ((vt[v] & 7) == 0) {
       pE[j[v]] = plan32_prune_E(plan32_prune_dn(a.xxmax), row[v] ? ec[v] : 0.0);
       ph[j[v]] = row[v] ? plan32_prune_h(sm[v], ec[v], ecmax) : INFINITY;
+      // the direct test's neighbours (screen32bs; rows past k: none)
+      plan32_near(nk[v], row[v] ? ec[v] : 0.0, ecmax, pc + j[v] * kPrStr);
     }
   }
   for (int idx = t; idx < MT * 64; idx += NT) {  // the layout of plan32_lane

@@ -1050,6 +1050,7 @@ float* g_dbg_ptr = nullptr;  // set by cdr_debug_screen (tests only)
 float g_dbg_thr[2] = {0.f, 0.f};
 
 bool screen32_supported(const Ctx& c, int k);
+void debug_plan32(Ctx& c, int which, const double* C, int k, float* out);
 bool big_step(Ctx& c, const double* C, int k, long long* dout, bool prof);
 bool screen32_step(Ctx& c, const double* C, int k, long long* dout, long long* hout, bool prof,
                    float* dbg, float* thr_out, long long* gate);
@@ -1943,6 +1944,15 @@ int cdr_lloyd_screen_layout(cdr_ctx* h, int32_t out[6]) {
   CDR_TRY
   if (!h || !out) CDR_FAIL(CDR_ERR_ARG, "null argument");
   for (int i = 0; i < 6; ++i) out[i] = h->c.s32_layout[i];
+  CDR_CATCH
+}
+
+// Test hook: the screen32 plan's prune block of centroids C (screen32.hip).
+int cdr_debug_plan32(cdr_ctx* h, int32_t which, const double* C, int32_t k, float* out) {
+  CDR_TRY
+  if (!h || !out) CDR_FAIL(CDR_ERR_ARG, "null argument");
+  HIP_CHECK(hipSetDevice(h->c.device));
+  debug_plan32(h->c, which, C, k, out);
   CDR_CATCH
 }
 

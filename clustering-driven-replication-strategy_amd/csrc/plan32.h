@@ -14,7 +14,8 @@ typedef _Float16 plan_h8 __attribute__((ext_vector_type(8)));
 // Plan buffer layout (host upload and device plan alike):
 //   frag [MT][2][64] h8 | cinit [MT][16][64] f32 | C copy k x d f64 |
 //   thr0, D (f32; device plan) | prune block (16-byte aligned):
-//   c32 [64][kPrStr] f32 | E [64] f32 | h [64] f32  (screen32p, plan32_prune)
+//   c32 [64][kPrStr] f32 | E [64] f32 | h [64] f32  (screen32p, plan32_prune;
+//   columns 16-19 of a c32 row: the direct test's n1, n2, h3, ec32, below)
 constexpr int kPrStr = 20;  // c32 row stride in floats (16-byte aligned rows)
 constexpr size_t kPrBytes = sizeof(float) * (64 * kPrStr + 64 + 64);
 struct Plan32Layout {
@@ -87,6 +88,41 @@ __host__ __device__ inline float plan32_prune_h(double smin, double ec_r, double
   if (!(smin < INFINITY)) return INFINITY;
   const double lo = sqrt(smin) * (1.0 - ldexp(1.0, -44)) - ec_r - ecmax;
   return lo > 0.0 ? (float)(lo * (1.0 - ldexp(1.0, -22))) : 0.0f;
+}
+
+// The direct test's values of centroid r (screen32bs), in the
+// four spare floats of its c32 row: the indices n1, n2 of the two nearest
+// other centroids (int bits; -1: none), h3_r = a rounded-down lower bound of
+// the third-smallest ||chat_r - chat_q|| (+inf with fewer than three other
+// centroids) and ec32_r >= ||c32_r - chat_r||.
+constexpr int kPrN1 = 16, kPrN2 = 17, kPrH3 = 18, kPrEc = 19;
+// A pair's key: the squared distance's fp64 bits (>= 0: the bits order as the
+// values) with the low 6 replaced by the other centroid's index, so equal
+// distances order by index and every builder keeps the same three.  The
+// value read back from a key is the distance rounded down by < 2^-46
+// relative, inside plan32_prune_h's margin.
+typedef unsigned long long plan_key;
+constexpr plan_key kPlanNoKey = 0x7FF0000000000000ull;  // +inf: no centroid
+__host__ __device__ inline plan_key plan32_key(double s2, int q) {
+  return (__builtin_bit_cast(plan_key, s2) & ~63ull) | (plan_key)(unsigned)q;
+}
+// the three smallest keys, in order (insertion; a merge inserts the other
+// list's three: min / max of distinct keys, any order gives the same three)
+__host__ __device__ inline void plan32_top3(plan_key (&t)[3], plan_key key) {
+  const plan_key a = key < t[0] ? t[0] : key;
+  t[0] = key < t[0] ? key : t[0];
+  const plan_key b = a < t[1] ? t[1] : a;
+  t[1] = a < t[1] ? a : t[1];
+  t[2] = b < t[2] ? b : t[2];
+}
+__host__ __device__ inline void plan32_near(const plan_key (&t)[3], double ec_r, double ecmax,
+                                            float* row) {
+  int n[2];
+  for (int i = 0; i < 2; ++i) n[i] = (t[i] & ~63ull) < kPlanNoKey ? (int)(t[i] & 63ull) : -1;
+  row[kPrN1] = __builtin_bit_cast(float, n[0]);
+  row[kPrN2] = __builtin_bit_cast(float, n[1]);
+  row[kPrH3] = plan32_prune_h(__builtin_bit_cast(double, t[2] & ~63ull), ec_r, ecmax);
+  row[kPrEc] = (float)(ec_r * (1.0 + ldexp(1.0, -20)));
 }
 
 // Certification constants from the centroid side (ccmax =
@@ -260,6 +296,7 @@ __device__ inline void plan32_build(const double* __restrict__ C, int k, int d, 
   __shared__ float c32[64 * 16];
   __shared__ double pec[64];
   __shared__ unsigned long long smin_b[64], ecmax_b;
+  __shared__ plan_key near_b[4][64][3];  // the column groups' three nearest of every row
   if (t == 0) ecmax_b = 0ull;
   for (int e = t; e < 64 * kPrStr; e += blockDim.x) {
     const int j = e / kPrStr, f = e - j * kPrStr;
@@ -285,9 +322,11 @@ __device__ inline void plan32_build(const double* __restrict__ C, int k, int d, 
     if (t < k) atomicMax(&ecmax_b, (unsigned long long)__double_as_longlong(ec));
   }
   {  // row r = t % 64, columns j = t / 64 + G i: the smallest squared distance
-    const int r = t & 63, G = blockDim.x >> 6;
+    // (the first 4 column groups cover every column: G = min(blockDim / 64, 4))
+    const int r = t & 63, G = blockDim.x >> 6 < 4 ? blockDim.x >> 6 : 4;
     double sm = INFINITY;
-    if (r < k)
+    plan_key t3[3] = {kPlanNoKey, kPlanNoKey, kPlanNoKey};
+    if (r < k && (t >> 6) < G)
       for (int j = t >> 6; j < k; j += G) {
         if (j == r) continue;
         double s2 = 0.0;
@@ -296,14 +335,23 @@ __device__ inline void plan32_build(const double* __restrict__ C, int k, int d, 
           s2 += df * df;
         }
         sm = fmin(sm, s2);
+        plan32_top3(t3, plan32_key(s2, j));
       }
     atomicMin(&smin_b[r], (unsigned long long)__double_as_longlong(sm));  // >= 0: bits order
+    if ((t >> 6) < 4)
+      for (int i = 0; i < 3; ++i) near_b[t >> 6][r][i] = t3[i];
   }
   __syncthreads();
-  if (t < 64)
-    ph[t] = t < k ? plan32_prune_h(__longlong_as_double(smin_b[t]), pec[t],
-                                   __longlong_as_double(ecmax_b))
-                  : INFINITY;
+  if (t < 64) {
+    const double ecmax = __longlong_as_double(ecmax_b);
+    ph[t] = t < k ? plan32_prune_h(__longlong_as_double(smin_b[t]), pec[t], ecmax) : INFINITY;
+    // the direct test's neighbours (screen32bs; rows past k: none)
+    plan_key t3[3] = {kPlanNoKey, kPlanNoKey, kPlanNoKey};
+    const int G = blockDim.x >> 6 < 4 ? blockDim.x >> 6 : 4;
+    for (int g = 0; g < G; ++g)
+      for (int i = 0; i < 3; ++i) plan32_top3(t3, near_b[g][t][i]);
+    plan32_near(t3, t < k ? pec[t] : 0.0, ecmax, pc + t * kPrStr);
+  }
 }
 
 }  // namespace cdr

@@ -241,6 +241,7 @@ static bool build_plan32(const Ctx& c, const double* C, int k, Plan32& pl) {
   }
   for (int r = 0; r < 64; ++r) {
     double sm = INFINITY;
+    plan_key t3[3] = {kPlanNoKey, kPlanNoKey, kPlanNoKey};
     for (int j = 0; j < k && r < k; ++j) {
       if (j == r) continue;
       double s2 = 0.0;
@@ -249,8 +250,11 @@ static bool build_plan32(const Ctx& c, const double* C, int k, Plan32& pl) {
         s2 += df * df;
       }
       sm = std::fmin(sm, s2);
+      plan32_top3(t3, plan32_key(s2, j));
     }
     ph[r] = r < k ? plan32_prune_h(sm, ec[r], ecmax) : INFINITY;
+    // the direct test's neighbours (screen32bs; rows past k: none)
+    plan32_near(t3, r < k ? ec[r] : 0.0, ecmax, pc + r * kPrStr);
   }
   return true;
 }
@@ -274,6 +278,50 @@ void plan32_launch(Ctx& c, int k, int QH, int MT) {
                      QH, MT, c.ll_ref.as<double>() + c.d, std::ldexp(1.0, c.sigma), c.ll_xxmax,
                      c.ll_l1x, c.ll_state.as<long long>(), static_cast<unsigned char*>(c.frag.p));
   HIP_CHECK(hipGetLastError());
+}
+
+// Test hook (cdr_debug_plan32): the prune block (plan32.h: kPrBytes) of
+// centroids C from the host plan (which = 0) or plan32_kernel (1), or the one
+// the device loop's last finalize left in the plan buffer (2; C unused).
+void debug_plan32(Ctx& c, int which, const double* C, int k, float* out) {
+  const int d = c.d;
+  if (c.mode != CDR_MODE_F32X || d > 16 || k < 1 || k > 64)
+    CDR_FAIL(CDR_ERR_UNSUPPORTED, "no screen32 plan for this shape");
+  const int QH = d4_of(d) / 4 <= 2 ? 1 : 2, MT = k <= 32 ? 1 : 2;
+  const Plan32Layout L = plan32_layout(MT, k, d);
+  if (which == 0) {
+    Plan32 pl;
+    if (!C || !build_plan32(c, C, k, pl)) CDR_FAIL(CDR_ERR_ARG, "centroids out of the plan's range");
+    std::memcpy(out, pl.prune.data(), kPrBytes);
+  } else if (which == 1) {
+    if (!C) CDR_FAIL(CDR_ERR_ARG, "null centroids");
+    DevBuf dC, dmu, dst, dplan;
+    std::vector<double> mu(d);
+    for (int f = 0; f < d; ++f) mu[f] = (double)c.mu[f];
+    const long long st[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+    dC.ensure(sizeof(double) * (size_t)k * d);
+    dmu.ensure(sizeof(double) * d);
+    dst.ensure(sizeof(st));
+    dplan.ensure(L.all);
+    HIP_CHECK(hipMemcpyAsync(dC.p, C, sizeof(double) * (size_t)k * d, hipMemcpyHostToDevice, c.stream));
+    HIP_CHECK(hipMemcpyAsync(dmu.p, mu.data(), sizeof(double) * d, hipMemcpyHostToDevice, c.stream));
+    HIP_CHECK(hipMemcpyAsync(dst.p, st, sizeof(st), hipMemcpyHostToDevice, c.stream));
+    double xxmax, l1x;
+    plan32_point_side(c, xxmax, l1x);
+    hipLaunchKernelGGL(plan32_kernel, dim3(1), dim3(256), 0, c.stream, dC.as<double>(), k, d, QH, MT,
+                       dmu.as<double>(), std::ldexp(1.0, c.sigma), xxmax, l1x, dst.as<long long>(),
+                       static_cast<unsigned char*>(dplan.p));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, static_cast<unsigned char*>(dplan.p) + L.prune, kPrBytes,
+                             hipMemcpyDeviceToHost, c.stream));
+    HIP_CHECK(hipStreamSynchronize(c.stream));
+    for (DevBuf* b : {&dC, &dmu, &dst, &dplan}) b->release();
+  } else {
+    if (!c.ll_on || c.frag.bytes < L.all) CDR_FAIL(CDR_ERR_STATE, "no device loop plan");
+    HIP_CHECK(hipMemcpyAsync(out, static_cast<unsigned char*>(c.frag.p) + L.prune, kPrBytes,
+                             hipMemcpyDeviceToHost, c.stream));
+    HIP_CHECK(hipStreamSynchronize(c.stream));
+  }
 }
 
 // Build the exact pre-centred copy xt = (x - mu) 2^sigma once per point set
@@ -595,10 +643,14 @@ static void screen32_delta_step(Ctx& c, int QH, int MT, int k, const h8* dfrag,
     b.zh = z16 ? c.zb.as<uint16_t>() : nullptr;
     b.bt = reinterpret_cast<const unsigned char*>(c.bnd.p);
     b.t_acc = c.prof_on ? c.t_acc.as<long long>() : nullptr;
-    b.dbg = exp_env("CDR_BOUNDS_DBG") ? std::atoi(exp_env("CDR_BOUNDS_DBG")) : 0;
+    // (a test switch, read on every call: bit 0 makes every bound fail)
+    b.dbg = std::getenv("CDR_BOUNDS_DBG") ? std::atoi(std::getenv("CDR_BOUNDS_DBG")) : 0;
 #ifndef CDR_EXPERIMENTS
     b.dbg &= 1;  // (the other bits are timing experiments: experiments build only)
 #endif
+    // screen32bs's direct test; CDR_S32BS_DIRECT=0 (tests, A/B):
+    // the triangle test and the split screen decide, read on every call
+    b.direct = !std::getenv("CDR_S32BS_DIRECT") || std::atoi(std::getenv("CDR_S32BS_DIRECT"));
     c.zb_valid = true;
     b.tprof = nullptr;
     b.slot_wg = 0;

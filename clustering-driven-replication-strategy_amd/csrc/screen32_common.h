@@ -180,6 +180,7 @@ struct S32BArgs {
   int64_t nchunks;           // n_pad / kBChunk
   long long* t_acc;          // profiling: points whose bound failed, per wave (null: off)
   int dbg;                   // tests only (CDR_BOUNDS_DBG): 1 = every bound fails
+  int direct;                // screen32bs: the direct test decides first (CDR_S32BS_DIRECT=0: off)
   unsigned long long* tprof; // experiments build only: per-wave timestamps (null: off)
   // screen32bs: chunk shares per CU slot (the workgroups blockIdx / slot_wg
   // = s share chunks [R_s, R_s+1) in proportion wsl[s]); slot_wg 0: one

@@ -8,10 +8,13 @@
 // transactions as screen32b's 32-byte hi row) and decides each batch of 64
 // without a queue, a list or a fixup pass:
 //   * xhat32 = fma(x, 2^sigma, -mu 2^sigma) (split_copy_kernel's values) and
-//     the triangle test against c32_a with q = ||xhat32 - c32_a||^2 (the same
-//     rounding count as screen32p's; E_a >= dn + ec covers ||xhat32 - xhat||
-//     + ||c32_a - chat_a||, as it covers the fp16 row);
-//   * when any lane of the batch fails it, the SPLIT screen of the whole batch
+//     the direct test: fp32 distances to c32_a and its two
+//     nearest centroids with rigorous intervals, every other centroid bounded
+//     through h3_a (CDR_S32BS_DIRECT=0: the triangle test against c32_a
+//     alone, E_a >= dn + ec covering ||xhat32 - xhat|| + ||c32_a - chat_a||);
+//   * a few undecided lanes of a batch go to the wave's tail list as "not
+//     screened" records; kDirectDense or more (and every undecided lane of
+//     the split form) take the SPLIT screen of the whole batch
 //     (the full screen's 2-3 MFMA per centroid tile on the hi / lo halves of
 //     xhat32, formed in registers: one permlane32 swap per operand dword turns
 //     the lanes' own rows into both 32-point B operands) and its
@@ -41,6 +44,18 @@ namespace cdr {
 #ifndef CDR_S32BS_LAZY
 #define CDR_S32BS_LAZY 1  // screen32bs: phase 2 interleaved with the stream (0: in bursts)
 #endif
+
+#ifndef CDR_S32BS_DENSE
+#define CDR_S32BS_DENSE 8  // kDirectDense (A/B at config 3: 4, 8, 16)
+#endif
+// A gathered batch with at least this many lanes the direct test leaves
+// undecided takes the in-batch split screen; with fewer, those lanes go to
+// the wave's tail list as "not screened" records
+constexpr int kDirectDense = CDR_S32BS_DENSE;
+// ... whose key no screen produces: the keys are fp32 bit patterns with the
+// low 6 bits cleared, and a NaN grown from fp16 operands has mantissa bits
+// 6-12 clear
+constexpr unsigned kNotScreened = 0xFFFFFFC0u;
 
 template <int Q, int MT, bool SPLIT = false>
 __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
@@ -172,7 +187,8 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
   __syncthreads();
   CDR_TP(1);
 
-  int fb_used = 0, mv_used = 0, qtot = 0, ttot = 0;
+  // (fb_used: the wave's tail records, fb_cert of them certified in the tail)
+  int fb_used = 0, fb_cert = 0, mv_used = 0, qtot = 0, ttot = 0;
   const f4* XA4 = reinterpret_cast<const f4*>(F.XA);  // point i: XA4[i * Q + q]
 
   // (best, runner-up) keys of one 32-point tile of the split screen
@@ -435,36 +451,109 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
     }
     return lab;
   };
+  // ||xhat32||^2 (fp32, 16 roundings at most: relative 2^-19 covers them)
+  auto norm2 = [&](const float (&xh)[DM]) __attribute__((always_inline)) -> float {
+    f2 acc = {0.0f, 0.0f};
+#pragma unroll
+    for (int f = 0; f < DM; f += 2) {
+      const f2 v = {xh[f], xh[f + 1]};
+      acc = __builtin_elementwise_fma(v, v, acc);
+    }
+    return acc.x + acc.y;
+  };
+  // K-case: a certified point's bounds from its split keys (vb, vs)
+  auto kcase = [&](float xx, float vb, float vs, float& u0, float& l0) __attribute__((always_inline)) {
+    const float xu = fmaf(xx, 1.0f + 0x1p-19f, 0x1p-120f);  // >= ||xhat32||^2
+    const float xl = xx * (1.0f - 0x1p-19f);               // <= ||xhat32||^2
+    const float dn32 = fmaf(0x1p-24f * (1.0f + 0x1p-20f), __builtin_amdgcn_sqrtf(xu), 0x1p-120f);
+    const float gb = fmaf(vb, thr_rel, thr0 + xu - Dlo);
+    const float gs = vs - ((thr0 + Dhi) - xl);
+    u0 = fmaf(__builtin_amdgcn_sqrtf(fmaxf(gb, 0.0f)), 1.0f + 0x1p-19f, dn32);
+    l0 = fmaf(__builtin_amdgcn_sqrtf(fmaxf(gs, 0.0f)), 1.0f - 0x1p-19f, -dn32);
+  };
   // one gathered batch: lane l decides point l
   auto decide = [&](const GB& g) __attribute__((always_inline)) {
     const bool valid = g.valid;
     const int pt = g.pt, ao = g.ao;
     float xh[DM];
     rowhat(g.x, xh);
-    // triangle test: q = ||xhat32 - c32_a||^2
     const float qa = q32(xh, ao);
-    const float uba = fmaf(__builtin_amdgcn_sqrtf(qa), 1.0f + 0x1p-18f, eb[ao]);
-    const float l0P = fmaf(hc[ao], 1.0f - 0x1p-22f, -uba);
-    const bool keep = l0P > uba * (1.0f + 0x1p-20f);
-    const float w_ao = __shfl(wnew_l, ao);
-    if (valid && keep) zput(pt, true, l0P, uba, w_ao, (unsigned)ao);
-    const bool need = valid && !keep;
+    const float xx = norm2(xh);
+    bool need;  // the lanes the k-way screen decides
+    if (B.direct) {
+      // The direct test: fp32 distances to c_ao and its two
+      // nearest centroids n1, n2 with near_tie's intervals, t_j within
+      // sqrt(q_j) (1 -+ 2^-19) -+ (dn32 + ec32_j); every other centroid j is
+      // at least ||chat_ao - chat_j|| - t_ao >= h3_ao - U_ao away.  Decided:
+      // the smallest root's upper end lies below every other lower end and
+      // that rest bound (a NaN decides nothing)
+      const f4 nv = reinterpret_cast<const f4*>(c32s + ao * kPrStr)[4];
+      const int n1 = __float_as_int(nv[kPrN1 - 16]), n2 = __float_as_int(nv[kPrN2 - 16]);
+      const float xu = fmaf(xx, 1.0f + 0x1p-19f, 0x1p-120f);
+      const float dn32 = fmaf(0x1p-24f * (1.0f + 0x1p-20f), __builtin_amdgcn_sqrtf(xu), 0x1p-120f);
+      int jb = ao;
+      float rbest = 0.0f, ub = 0.0f, lb_best = 0.0f, lo = INFINITY, ua = 0.0f;
+      bool bad = false;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {  // ao, n1, n2 ("none": +inf away)
+        const int jn = c == 0 ? ao : (c == 1 ? n1 : n2);
+        const bool none = (unsigned)jn >= 64u;  // (-1; anything else out of range too)
+        const int j = none ? ao : jn;
+        const float q = c == 0 ? qa : (none ? INFINITY : q32(xh, j));
+        const float ec = c == 0 ? nv[kPrEc - 16] : c32s[j * kPrStr + kPrEc];
+        const float e2 = (dn32 + ec) * (1.0f + 0x1p-20f);
+        const float r = __builtin_amdgcn_sqrtf(q);
+        const float U = fmaf(r, 1.0f + 0x1p-19f, e2), L = fmaf(r, 1.0f - 0x1p-19f, -e2);
+        bad = bad || !(U == U) || !(L == L);
+        if (c == 0) {
+          rbest = r;
+          ub = ua = U;
+          lb_best = L;
+        } else if (r < rbest) {
+          lo = fminf(lo, lb_best);
+          rbest = r;
+          ub = U;
+          lb_best = L;
+          jb = j;
+        } else {
+          lo = fminf(lo, L);
+        }
+      }
+      const float l0 = fminf(lo, fmaf(nv[kPrH3 - 16], 1.0f - 0x1p-22f, -ua));
+      const bool dec = !bad && l0 > ub * (1.0f + 0x1p-20f);
+      const float w_b = __shfl(wnew_l, jb);
+      if (valid && dec) zput(pt, true, l0, ub, w_b, (unsigned)jb);
+      move(valid && dec, pt, ao, jb, g.x);
+      need = valid && !dec;
+    } else {
+      // (CDR_S32BS_DIRECT=0) the triangle test: q = ||xhat32 - c32_a||^2
+      const float uba = fmaf(__builtin_amdgcn_sqrtf(qa), 1.0f + 0x1p-18f, eb[ao]);
+      const float l0P = fmaf(hc[ao], 1.0f - 0x1p-22f, -uba);
+      const bool keep = l0P > uba * (1.0f + 0x1p-20f);
+      const float w_ao = __shfl(wnew_l, ao);
+      if (valid && keep) zput(pt, true, l0P, uba, w_ao, (unsigned)ao);
+      need = valid && !keep;
+    }
     const unsigned long long nm = __ballot(need);
     if (!nm) return;
     qtot += __popcll(nm);
 #ifdef CDR_EXPERIMENTS
     if (B.dbg & 8) return;  // (timing: no k-way screen)
 #endif
-    // ||xhat32||^2 (fp32, 16 roundings at most: relative 2^-19 covers them)
-    float xx;
-    {
-      f2 acc = {0.0f, 0.0f};
-#pragma unroll
-      for (int f = 0; f < DM; f += 2) {
-        const f2 v = {xh[f], xh[f + 1]};
-        acc = __builtin_elementwise_fma(v, v, acc);
+    if constexpr (DEFER) {
+      // a few undecided lanes: "not screened" records (the old label in the
+      // key's low bits), screened with the tail's batches
+      if (B.direct && __popcll(nm) < kDirectDense) {
+        if (need) {
+          const int r = __builtin_amdgcn_mbcnt_hi((unsigned)(nm >> 32),
+                                                  __builtin_amdgcn_mbcnt_lo((unsigned)nm, 0u));
+          fb_region[fb_used + r] = int2{pt, (int)(kNotScreened | (unsigned)ao)};
+        }
+        // (readfirstlane: also keeps this update apart from the other counters',
+        // which the compiler otherwise merges into one indexed stack slot)
+        fb_used = __builtin_amdgcn_readfirstlane(fb_used + __popcll(nm));
+        return;
       }
-      xx = acc.x + acc.y;
     }
     unsigned bA, sA_;
     u4v T0[QH], T1[QH];
@@ -478,13 +567,8 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
     const float w_lab = __shfl(wnew_l, label);
     // K-case: the point's bound word from its split keys
     if (need && cert) {
-      const float xu = fmaf(xx, 1.0f + 0x1p-19f, 0x1p-120f);  // >= ||xhat32||^2
-      const float xl = xx * (1.0f - 0x1p-19f);               // <= ||xhat32||^2
-      const float dn32 = fmaf(0x1p-24f * (1.0f + 0x1p-20f), __builtin_amdgcn_sqrtf(xu), 0x1p-120f);
-      const float gb = fmaf(vb, thr_rel, thr0 + xu - Dlo);
-      const float gs = vs - ((thr0 + Dhi) - xl);
-      const float u0 = fmaf(__builtin_amdgcn_sqrtf(fmaxf(gb, 0.0f)), 1.0f + 0x1p-19f, dn32);
-      const float l0 = fmaf(__builtin_amdgcn_sqrtf(fmaxf(gs, 0.0f)), 1.0f - 0x1p-19f, -dn32);
+      float u0, l0;
+      kcase(xx, vb, vs, u0, l0);
       zput(pt, true, l0, u0, w_lab, (unsigned)label);
     }
     const unsigned long long um = __ballot(unc);
@@ -834,8 +918,8 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
 #endif
   if constexpr (DEFER) {
   // the next batch's records and rows load while one is decided
-  // (Q = 4: the records only - the rows ahead too spill registers)
-  constexpr int QA = Q < 4 ? Q : 0;
+  // (Q >= 3: the records only - the rows ahead too spill registers)
+  constexpr int QA = Q < 3 ? Q : 0;
   auto tload = [&](int e0, int2& rec, f4 (&xr)[Q]) __attribute__((always_inline)) {
     const int e = e0 + lane;
     rec = fb_region[e < fb_used ? e : e0];
@@ -861,27 +945,48 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
     rowhat(xr, xh);
     u4v T0[QH], T1[QH];
     split_tiles(xh, T0, T1);
-    float xx;
-    {
-      f2 acc = {0.0f, 0.0f};
-#pragma unroll
-      for (int f = 0; f < DM; f += 2) {
-        const f2 v = {xh[f], xh[f + 1]};
-        acc = __builtin_elementwise_fma(v, v, acc);
+    const float xx = norm2(xh);
+    // "not screened" records (the direct test's few undecided lanes): the
+    // split screen and its certificate now, the K-case word for the
+    // certified; the others join the near ties with their best key
+    unsigned bkey = (unsigned)rec.y;
+    const bool uns = live && (bkey & ~63u) == kNotScreened;
+    bool tie = live;
+    int lab = ao;
+    if (__ballot(uns)) {
+      unsigned bA, sA_;
+      keys(T0, T1, bA, sA_);
+      const float vb = __uint_as_float(bA & ~63u);
+      const float vs = __uint_as_float(sA_ & ~63u);
+      const bool cert = uns && vs > fmaf(vb, thr_rel, thr0);  // NaN: never certified
+      const float w_c = __shfl(wnew_l, (int)(bA & 63u));
+      if (uns) bkey = bA;
+      if (cert) {
+        float u0, l0;
+        kcase(xx, vb, vs, u0, l0);
+        lab = (int)(bA & 63u);
+        zput(pt, true, l0, u0, w_c, (unsigned)lab);
+        tie = false;
       }
-      xx = acc.x + acc.y;
+      fb_cert += __popcll(__ballot(cert));
     }
-    bool c2;
-    float u0, l0;
-    const int lab = near_tie(live, ao, (unsigned)rec.y, xh, T0, T1, xr, xx, c2, u0, l0);
-    const float w_lab = __shfl(wnew_l, lab);
-    if (live) zput(pt, c2, l0, u0, w_lab, (unsigned)lab);  // the direct bounds, or none
+    const unsigned long long tm = __ballot(tie);
+    if (tm) {
+      bool c2;
+      float u0, l0;
+      const int lt = near_tie(tie, ao, bkey, xh, T0, T1, xr, xx, c2, u0, l0);
+      const float w_lab = __shfl(wnew_l, lt);
+      if (tie) {
+        lab = lt;
+        zput(pt, c2, l0, u0, w_lab, (unsigned)lab);  // the direct bounds, or none
+      }
+    }
     move(live, pt, ao, lab, xr);
   }
   }  // DEFER
   CDR_TP(3);
   if (lane == 0) {
-    a.fb_count[wave] = fb_used;
+    a.fb_count[wave] = fb_used - fb_cert;  // the points no certificate decided
     a.mv_count[wave] = mv_used;
     if (a.q_acc) a.q_acc[wave] += qtot;
     if (B.t_acc) B.t_acc[wave] += ttot;

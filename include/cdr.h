@@ -345,6 +345,12 @@ int cdr_lloyd_screen_layout(cdr_ctx* ctx, int32_t out[6]);
  * of one F32X step and the certification constants (A0, A1).               */
 int cdr_debug_screen(cdr_ctx* ctx, const double* C, int32_t k, float* out_vals,
                      float* thr_a0a1);
+/* Test hook: the screen32 plan's prune block (64 rows of 20 floats: the fp32
+ * centroid, then the direct test's n1, n2 (int32 bits), h3, ec32; then E[64]
+ * and h[64]) of centroids C (k, d) from the host plan (which = 0) or the
+ * device plan kernel (1), or as the device loop's last finalize left it (2; C
+ * unused); out: 1408 floats.                                                 */
+int cdr_debug_plan32(cdr_ctx* ctx, int32_t which, const double* C, int32_t k, float* out);
 
 /* ---- per-cluster medians: src/scoring.py:40-55 (np.median) ------------- */
 /* Segmented median of float64 values: segment s = values[off[s]..off[s+1]).
