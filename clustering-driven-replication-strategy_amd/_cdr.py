@@ -94,6 +94,8 @@ SIGNATURES = {
     "cdr_f64s_chain": ([_P, _P], None),
     "cdr_profile_kernel": ([_P, _P, _I32], None),
     "cdr_lloyd_screen_layout": ([_P, _P], None),
+    "cdr_lloyd_big_layout": ([_P, _P], None),
+    "cdr_debug_big_plan": ([_P, _I32, _P, _I64, _PI64], None),
     "cdr_points_sqdev": ([_P, _P, _PF64], None),
     "cdr_lloyd_begin": ([_P, _P, _I32, _F64, _I32, _P, _F64], None),
     "cdr_lloyd_enqueue_assign": ([_P, _P], None),
@@ -597,6 +599,33 @@ class Context:
         _check(self._lib.cdr_lloyd_screen_layout(self._h, _ptr(out)))
         names = ("workgroups", "slot_wg", "dyn_pct", "max_chunks", "nchunks", "word_bytes")
         return {nm: int(v) for nm, v in zip(names, out)}
+
+    def big_layout(self) -> dict:
+        """What the last large-k step chose and counted (cdr_lloyd_big_layout);
+        every value 0 when none has run since the points were loaded."""
+        out = np.zeros(15, dtype=np.int64)
+        _check(self._lib.cdr_lloyd_big_layout(self._h, _ptr(out)))
+        names = ("DQ", "KB", "FG", "JB", "l1_threads", "l2_form", "delta", "plan", "regions",
+                 "cap1", "groups", "leftovers", "l3", "mv1", "mv2")
+        return {nm: int(v) for nm, v in zip(names, out)}
+
+    def debug_big_plan(self, k: int) -> dict:
+        """The plan buffer of the last large-k step of k centroids
+        (cdr_debug_big_plan): frag1 and cinit as raw bytes, C (k, d) float64
+        and thr = float32 {thr1, thr_rel}."""
+        d = self.info()["d"]
+        dq, kb = -(-d // 16), -(-int(k) // 32)
+        b1, bc, bC = kb * dq * 64 * 16, kb * 32 * 4, 8 * int(k) * d
+        got = _I64()
+        _check(self._lib.cdr_debug_big_plan(self._h, int(k), None, 0, ctypes.byref(got)))
+        if got.value != b1 + bc + bC + 16:
+            raise RuntimeError(f"debug_big_plan: {got.value} bytes, expected {b1 + bc + bC + 16}")
+        raw = np.empty(got.value, dtype=np.uint8)
+        _check(self._lib.cdr_debug_big_plan(self._h, int(k), _ptr(raw), raw.size,
+                                            ctypes.byref(got)))
+        return {"frag1": raw[:b1].copy(), "cinit": raw[b1:b1 + bc].copy(),
+                "C": raw[b1 + bc:b1 + bc + bC].copy().view(np.float64).reshape(int(k), d),
+                "thr": raw[b1 + bc + bC:b1 + bc + bC + 8].copy().view(np.float32)}
 
     # -- device-resident Lloyd loop (csrc/loop.hip) ---------------------------
     LL_RUNNING, LL_CONVERGED, LL_EMPTY, LL_HOST_PLAN, LL_AMBIGUOUS = 0, 1, 2, 3, 4

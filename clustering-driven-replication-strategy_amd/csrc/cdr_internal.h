@@ -158,6 +158,11 @@ struct Ctx {
   DevBuf big_chunks;  // L2 chunk numbering of L1's regions (big_chunk_prefix)
   bool big_valid = false;
   int big_k = 0;
+  // the last large-k launch (cdr_lloyd_big_layout): DQ, KB, FG, JB, L1 threads,
+  // L2 form (0 cand_big_lds, 1 cand_big), delta, L1 regions, cap1, 64-point
+  // groups, plan (0 host, 1 device); zeros: none since the points were loaded
+  int64_t big_info[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  float big_thr_host[2] = {0.f, 0.f};  // {thr1, thr_rel} of that launch's host plan
   bool xs_valid = false;  // xs16 built (ensure_split)
   DevBuf mv_list;   // screen32p / screen32b: per-wave regions of moved points {pt, old | new << 16}
   DevBuf mv_count;  // int32 per wave

@@ -303,6 +303,7 @@ static void decide_mode(Ctx& c, const std::vector<unsigned long long>& st,
   c.lab8_valid = false;
   c.zb_valid = false;
   c.big_valid = false;
+  for (int64_t& v : c.big_info) v = 0;  // no large-k step on these points yet
   c.seed_scanned = false;
 }
 
@@ -324,6 +325,7 @@ static void reset_points(Ctx& c, int64_t n, int32_t d) {
   c.xb_valid = false;
   c.xa_valid = false;
   c.big_valid = false;
+  for (int64_t& v : c.big_info) v = 0;
   c.pre_ok = false;
   c.n = n;
   c.d = d;

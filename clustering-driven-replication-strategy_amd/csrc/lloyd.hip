@@ -1051,6 +1051,8 @@ float g_dbg_thr[2] = {0.f, 0.f};
 
 bool screen32_supported(const Ctx& c, int k);
 void debug_plan32(Ctx& c, int which, const double* C, int k, float* out);
+void big_layout_read(Ctx& c, int64_t out[15]);                        // screen_big.hip
+int64_t debug_big_plan(Ctx& c, int k, void* out, int64_t bytes);     // screen_big.hip
 bool big_step(Ctx& c, const double* C, int k, long long* dout, bool prof);
 bool screen32_step(Ctx& c, const double* C, int k, long long* dout, long long* hout, bool prof,
                    float* dbg, float* thr_out, long long* gate);
@@ -1257,14 +1259,15 @@ void lloyd_step_f32x(Ctx& c, const double* C, int32_t k, int64_t* out, bool out_
     c.lab8_valid = false;
     c.zb_valid = false;
     c.big_valid = false;
+    // the update table of large k without screen_big (pre_ok false) takes more
+    // than the default 64 KiB of dynamic LDS; a workgroup can have 160 KiB.
+    // Checked before the assignment, so an unsupported shape launches no kernel
+    const size_t lds = (size_t)len * 8;
+    if (lds > 160 * 1024) CDR_FAIL(CDR_ERR_UNSUPPORTED, "k*(d+1) too large for the update table");
     // exact assignment for every point, then fixed-point sums from labels
     launch_assign_exact<float>(c.x32.as<float>(), c.n, c.n_pad, d, c.cent64.as<double>(), k,
                                c.labels.as<int32_t>(), cus, c.stream);
     snprintf(c.prof_kernel, sizeof(c.prof_kernel), "assign_exact_all<%d>", d);
-    // the update table of large k without screen_big (pre_ok false) takes more
-    // than the default 64 KiB of dynamic LDS; a workgroup can have 160 KiB
-    const size_t lds = (size_t)len * 8;
-    if (lds > 160 * 1024) CDR_FAIL(CDR_ERR_UNSUPPORTED, "k*(d+1) too large for the update table");
     static bool uattr = false;
     if (!uattr) {
       HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&update_from_labels_f32x),
@@ -1953,6 +1956,23 @@ int cdr_debug_plan32(cdr_ctx* h, int32_t which, const double* C, int32_t k, floa
   if (!h || !out) CDR_FAIL(CDR_ERR_ARG, "null argument");
   HIP_CHECK(hipSetDevice(h->c.device));
   debug_plan32(h->c, which, C, k, out);
+  CDR_CATCH
+}
+
+int cdr_lloyd_big_layout(cdr_ctx* h, int64_t out[15]) {
+  CDR_TRY
+  if (!h || !out) CDR_FAIL(CDR_ERR_ARG, "null argument");
+  HIP_CHECK(hipSetDevice(h->c.device));
+  big_layout_read(h->c, out);
+  CDR_CATCH
+}
+
+// Test hook: the large-k plan buffer of the last large-k step (screen_big.hip).
+int cdr_debug_big_plan(cdr_ctx* h, int32_t k, void* out, int64_t bytes, int64_t* written) {
+  CDR_TRY
+  if (!h || !written) CDR_FAIL(CDR_ERR_ARG, "null argument");
+  HIP_CHECK(hipSetDevice(h->c.device));
+  *written = debug_big_plan(h->c, k, out, bytes);
   CDR_CATCH
 }
 

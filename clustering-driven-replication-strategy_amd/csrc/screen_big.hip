@@ -18,7 +18,8 @@
 //      when runner > best (1 + 2^-18) + T1 (T1 = twice the rigorous bound on
 //      |S_j - exact shifted distance| + the reference's rounding slack);
 //      the rest go to per-wave regions.
-//  L2  cand_big<DQ>: the L1 leftovers, 64 per wave (chunks of L1's regions
+//  L2  cand_big_lds<DQ> (fragments in LDS) or, at the largest KB, cand_big<DQ>
+//      (fragments from global memory; see launch_big_levels): the L1 leftovers, 64 per wave (chunks of L1's regions
 //      numbered through an LDS prefix): the same one-product screen is
 //      recomputed and every centroid with S_j <= best (1 + 2^-18) + T1 is a
 //      candidate (the exact argmin is among them); each lane then takes one
@@ -718,9 +719,12 @@ __global__ __launch_bounds__(256) void cand_big(BigArgs a, const float* __restri
   }
 }
 
-// L2 with the A fragments and C rows in LDS (the product L2 after
-// screen_big_sp; cand_big reads them from global memory per chunk, 7x L1's
-// cost per point).  One NT-thread workgroup per CU; the chunk numbering of
+// L2 with the A fragments and C rows in LDS: the L2 after screen_big_sp
+// while the fragments and its candidate lists fit 160 KiB of LDS (L1's
+// lds1 <= 145,408 B).  Above that, up to big_supported's 150 KiB, the step
+// runs cand_big, which reads the fragments from global memory per chunk (7x
+// L1's cost per point): a product path too, e.g. d = 64, k = 1100 (KB 35..36
+// at DQ 4, 46..48 at DQ 3, 67..70 at DQ 2, 127..133 at DQ 1).  One NT-thread workgroup per CU; the chunk numbering of
 // L1's regions comes from big_chunk_prefix (global memory: the LDS holds the
 // fragments).  Per chunk of 64 points: the same one-product screen as L1
 // (bit-identical: same fragments, same B operands from xb16), candidates
@@ -1362,6 +1366,7 @@ static void launch_big_levels(Ctx& c, const BigArgs& a1, const BigArgs& a2, dim3
     // L2 on LDS-resident fragments: chunk numbering first (global), then
     // one workgroup per CU
     int32_t* pre = chunk_pre;
+    c.big_info[5] = 0;
     hipLaunchKernelGGL(big_chunk_prefix, dim3(1), dim3(1024), 0, c.stream, a2.in_count,
                        a2.in_regions, pre);
     static bool lattr = false;
@@ -1373,6 +1378,7 @@ static void launch_big_levels(Ctx& c, const BigArgs& a1, const BigArgs& a2, dim3
     hipLaunchKernelGGL((cand_big_lds<DQ, 512>), dim3(lloyd_num_cus(c.device)), dim3(512), lds2,
                        c.stream, a2, dC, pre, ovf, ovf_count);
   } else {
+    c.big_info[5] = 1;
     hipLaunchKernelGGL((cand_big<DQ>), g2, dim3(256), 0, c.stream, a2, c.x32.as<float>(), dC, ovf,
                        ovf_count, abl);
   }
@@ -1588,6 +1594,20 @@ static bool big_launch(Ctx& c, int k, float thr1, float thr_rel, const float* th
   c.big_sums.ensure(sizeof(long long) * len);
   unsigned long long* bs = c.big_sums.as<unsigned long long>();
   const int FG = big_fg(k);
+  // what this launch chose (cdr_lloyd_big_layout); [5], the L2 form, is set
+  // by launch_big_levels
+  c.big_info[0] = DQ;
+  c.big_info[1] = KB;
+  c.big_info[2] = FG;
+  c.big_info[3] = JB;
+  c.big_info[4] = wpb1 * 64;
+  c.big_info[6] = delta ? 1 : 0;
+  c.big_info[7] = nw1;
+  c.big_info[8] = cap1;
+  c.big_info[9] = groups;
+  c.big_info[10] = thr_dev ? 1 : 0;
+  c.big_thr_host[0] = thr1;
+  c.big_thr_host[1] = thr_rel;
   const int ngrp = (d + FG - 1) / FG;
   const size_t ldsu = (size_t)FG * k * 8 + (size_t)k * 4;
   static bool uattr = false;
@@ -1638,6 +1658,61 @@ static bool big_launch(Ctx& c, int k, float thr1, float thr_rel, const float* th
   c.lab8_valid = false;
   c.zb_valid = false;
   return true;
+}
+
+// cdr_lloyd_big_layout (tests): what the last big_launch chose, and what its
+// levels counted.  out = {DQ, KB, FG, JB, L1 threads, L2 form, delta, plan,
+// L1 regions, cap1, groups, L1 leftovers, L3 points, mv1 moves, mv2 moves}.
+// The counters are read from the launch's own buffers after a stream
+// synchronise here, never on the step's path: they are those of the last
+// large-k step only until another step of the context reuses the buffers.
+void big_layout_read(Ctx& c, int64_t out[15]) {
+  for (int i = 0; i < 15; ++i) out[i] = 0;
+  if (c.big_info[0] == 0) return;
+  for (int i = 0; i < 7; ++i) out[i] = c.big_info[i];
+  out[7] = c.big_info[10];
+  out[8] = c.big_info[7];
+  out[9] = c.big_info[8];
+  out[10] = c.big_info[9];
+  const size_t nw1 = (size_t)c.big_info[7];
+  const size_t cb = sizeof(int32_t) * (nw1 + 2);
+  if (c.fb_count.bytes < cb) return;
+  std::vector<int32_t> cnt(nw1 + 2), mv;
+  HIP_CHECK(hipMemcpyAsync(cnt.data(), c.fb_count.p, cb, hipMemcpyDeviceToHost, c.stream));
+  const bool delta = c.big_info[6] != 0 && c.mv_count.bytes >= cb;
+  if (delta) {
+    mv.resize(nw1 + 2);
+    HIP_CHECK(hipMemcpyAsync(mv.data(), c.mv_count.p, cb, hipMemcpyDeviceToHost, c.stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(c.stream));
+  out[11] = cnt[nw1];
+  out[12] = cnt[nw1 + 1];
+  if (delta) {
+    for (size_t w = 0; w < nw1; ++w) out[13] += mv[w];
+    out[14] = mv[nw1];
+  }
+}
+
+// cdr_debug_big_plan (tests): the plan buffer of the last large-k step of k
+// centroids, frag1 | cinit | C | {thr1, thr_rel} (big_layout).  A host plan
+// passes its thresholds to the kernels by value; they are put in their slot
+// here.  Returns the bytes written; out may be null to ask for the size.
+int64_t debug_big_plan(Ctx& c, int k, void* out, int64_t bytes) {
+  if (c.big_info[0] == 0 || c.big_k != k)
+    CDR_FAIL(CDR_ERR_STATE, "debug_big_plan: the last large-k step was not of this k");
+  const BigLayout L = big_layout(k, c.d);
+  const size_t need = L.b1 + L.bc + L.bC + L.bt;
+  if (!out) return (int64_t)need;
+  if (bytes < (int64_t)need || c.frag.bytes < need)
+    CDR_FAIL(CDR_ERR_ARG, "debug_big_plan: buffer too small");
+  HIP_CHECK(hipMemcpyAsync(out, c.frag.p, need, hipMemcpyDeviceToHost, c.stream));
+  HIP_CHECK(hipStreamSynchronize(c.stream));
+  if (c.big_info[10] == 0) {
+    char* t = static_cast<char*>(out) + L.b1 + L.bc + L.bC;
+    memset(t, 0, L.bt);
+    memcpy(t, c.big_thr_host, sizeof(c.big_thr_host));
+  }
+  return (int64_t)need;
 }
 
 }  // namespace cdr

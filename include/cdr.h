@@ -341,6 +341,16 @@ int cdr_profile_kernel(cdr_ctx* ctx, char* buf, int32_t len);
  * statically, chunks, bytes per bound word (2 or 4)}; all zeros when no
  * bounded screen has run on the context.                                    */
 int cdr_lloyd_screen_layout(cdr_ctx* ctx, int32_t out[6]);
+/* What the context's last large-k step (screen_big.hip) chose and counted
+ * (tests): out = {DQ = ceil(d/16), KB = ceil(k/32), FG (features per update
+ * pass), JB (key bits holding the centroid index), L1 threads (512 or 768),
+ * L2 form (0: cand_big_lds, 1: cand_big), delta (0: full update pass, 1: moves
+ * only), plan (0: host, 1: device), L1 regions, capacity of a region, 64-point
+ * groups, L1 leftovers, points L3 decided, moves L1 recorded, moves L2 and L3
+ * recorded}; all zeros when no large-k step has run since the points were
+ * loaded.  The four counters are read back here, after a stream synchronise,
+ * from the step's own buffers: ask before the next step reuses them.         */
+int cdr_lloyd_big_layout(cdr_ctx* ctx, int64_t out[15]);
 /* Test hook (not product path): screen values T (n_pad, ceil(k/16)*16) fp32
  * of one F32X step and the certification constants (A0, A1).               */
 int cdr_debug_screen(cdr_ctx* ctx, const double* C, int32_t k, float* out_vals,
@@ -351,6 +361,13 @@ int cdr_debug_screen(cdr_ctx* ctx, const double* C, int32_t k, float* out_vals,
  * device plan kernel (1), or as the device loop's last finalize left it (2; C
  * unused); out: 1408 floats.                                                 */
 int cdr_debug_plan32(cdr_ctx* ctx, int32_t which, const double* C, int32_t k, float* out);
+/* Test hook: the plan buffer of the last large-k step, which must have been of
+ * k centroids: the fp16 A fragments (KB * DQ * 64 lanes of 16 bytes), the C
+ * operand rows (KB * 32 floats), the centroids (k * d doubles), then 16 bytes
+ * that begin with the floats {thr1, thr_rel}.  *written = the bytes; out may be
+ * null to ask for the size alone.  In a device loop the buffer holds the plan
+ * of the loop's current centroids.                                           */
+int cdr_debug_big_plan(cdr_ctx* ctx, int32_t k, void* out, int64_t bytes, int64_t* written);
 
 /* ---- per-cluster medians: src/scoring.py:40-55 (np.median) ------------- */
 /* Segmented median of float64 values: segment s = values[off[s]..off[s+1]).

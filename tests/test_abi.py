@@ -25,6 +25,8 @@ def test_every_declared_symbol_is_exported_and_bound():
     names = _declared()
     assert len(names) >= 25
     assert "cdr_lloyd_screen_layout" in names and hasattr(_cdr.Context, "screen_layout")
+    assert "cdr_lloyd_big_layout" in names and hasattr(_cdr.Context, "big_layout")
+    assert "cdr_debug_big_plan" in names and hasattr(_cdr.Context, "debug_big_plan")
     for name in names:
         assert hasattr(lib, name), name
         assert name in _cdr.SIGNATURES, f"{name} has no ctypes signature"
