@@ -139,6 +139,10 @@ SIGNATURES = {
     "cdr_quality_silhouette": ([_P, _P, _I64, _P, _I32, _P, _P, _P], None),
     "cdr_quality_scatter": ([_P, _P, _I32, _P, _P, _P], None),
     "cdr_quality_timing": ([_P, _P], None),
+    "cdr_csv_format": ([_P, _I64, _I32, ctypes.c_uint32, _P, _P, _P, _P, _I64, _PI64, _P, _I64,
+                        _PI64], None),
+    "cdr_csv_bound": ([_I64, _I32, _I64, _PI64], None),
+    "cdr_csv_timing": ([_P, _P], None),
     "cdr_host_seq_sum": ([_P, _I64, _F64], ctypes.c_double),
 }
 
@@ -971,6 +975,46 @@ class Context:
         if nf:
             _check(self._lib.cdr_features_finalize(self._h, nf, _ptr(counts), _ptr(creation_s),
                                                    float(observation_end), _ptr(out)))
+        return out
+
+    # -- features CSV on the device (csrc/csvout.hip) ------------------------
+    def csv_format(self, table, paths, long_cols=(), cap: int | None = None):
+        """The CSV rows ``path,cell,...,cell\n`` of table (n, n_cols) float64,
+        without a header: columns in long_cols as ``str(int(v))``, the others as
+        ``compute_features.java_double_legacy``, the path quoted as csv.writer
+        quotes it.  Returns (text as a uint8 array, deferred (m, 2) int64): a
+        deferred row (a cell outside the device range, a NUL or CR in the path;
+        include/cdr.h) has no bytes in the text and is listed as {row, byte
+        offset where its text belongs}.  ``cap``: size of the text buffer
+        (default: cdr_csv_bound, always enough)."""
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 2:
+            raise ValueError("table must be (rows, columns)")
+        n, n_cols = table.shape
+        if len(paths) != n:
+            raise ValueError("one path per table row")
+        mask = 0
+        for j in long_cols:
+            if not 0 <= int(j) < max(n_cols, 1):
+                raise ValueError("long column outside the table")
+            mask |= 1 << int(j)
+        pb, po = _pack_strings(paths)
+        if cap is None:
+            bound = _I64()
+            _check(self._lib.cdr_csv_bound(n, n_cols, int(po[-1]), ctypes.byref(bound)))
+            cap = int(bound.value)
+        out = np.empty(max(int(cap), 1), dtype=np.uint8)
+        deferred = np.empty((max(n, 1), 2), dtype=np.int64)
+        written, ndef = _I64(), _I64()
+        _check(self._lib.cdr_csv_format(self._h, n, n_cols, mask, _ptr(table), _ptr(pb), _ptr(po),
+                                        _ptr(out), int(cap), ctypes.byref(written),
+                                        _ptr(deferred), n, ctypes.byref(ndef)))
+        return out[:written.value], deferred[:ndef.value].copy()
+
+    def csv_timing(self) -> np.ndarray:
+        """{cell kernel, scan + emit kernels, copies} ms of the last csv_format."""
+        out = np.zeros(3, dtype=np.float64)
+        _check(self._lib.cdr_csv_timing(self._h, _ptr(out)))
         return out
 
 

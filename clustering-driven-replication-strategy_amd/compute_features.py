@@ -43,7 +43,9 @@ Spark semantics kept (Spark 3.5, docker/docker-compose.yml:67):
     the JDK that runs Spark: apache/spark:3.5.2 ships a pre-19 JDK, whose
     ``FloatingDecimal`` does not always print the shortest digits
     (``java_double_legacy``, the default).  ``CDR_JAVA_DOUBLE=19`` selects the
-    JDK 19+ shortest-digit layout (``java_double``).
+    JDK 19+ shortest-digit layout (``java_double``).  The pre-19 text is
+    formatted on the device (``write_spark_csv_device``, csrc/csvout.hip;
+    ``CDR_CSV_HOST=1`` keeps the host writer), byte-identical to the host's.
 """
 from __future__ import annotations
 
@@ -444,27 +446,116 @@ def compute_features(manifest: str, access_log: str, ctx: Context | None = None)
     return paths, table
 
 
-def write_spark_csv(out_dir: str, paths, table, fmt=None) -> str:
-    """One part file with a header, like ``coalesce(1).write.csv`` (:96).
-    ``fmt`` formats the doubles (default: ``CDR_JAVA_DOUBLE``, see above)."""
-    fmt = fmt or _double_formatter()
+def _begin_part(out_dir: str) -> tuple[str, str]:
+    """mode("overwrite") of the output directory; returns it and the path of
+    its one part file (not yet written)."""
     out_dir = _strip_scheme(out_dir)
     if os.path.isdir(out_dir):  # mode("overwrite")
         for name in os.listdir(out_dir):
             os.remove(os.path.join(out_dir, name))
     os.makedirs(out_dir, exist_ok=True)
-    part = os.path.join(out_dir, f"part-00000-{uuid.uuid4()}-c000.csv")
+    return out_dir, os.path.join(out_dir, f"part-00000-{uuid.uuid4()}-c000.csv")
+
+
+def _end_part(out_dir: str) -> None:
+    open(os.path.join(out_dir, "_SUCCESS"), "w").close()
+
+
+def _host_row(pth, values, fmt) -> list:
+    return [pth] + [str(int(values[j])) if col in LONG_COLUMNS else fmt(values[j])
+                    for j, col in enumerate(OUT_COLUMNS[1:])]
+
+
+def write_spark_csv(out_dir: str, paths, table, fmt=None) -> str:
+    """One part file with a header, like ``coalesce(1).write.csv`` (:96).
+    ``fmt`` formats the doubles (default: ``CDR_JAVA_DOUBLE``, see above)."""
+    fmt = fmt or _double_formatter()
+    out_dir, part = _begin_part(out_dir)
     with open(part, "w", newline="") as fh:
         w = csv.writer(fh, lineterminator="\n")
         w.writerow(OUT_COLUMNS)
         for i, pth in enumerate(paths):
-            row = [pth]
-            for j, col in enumerate(OUT_COLUMNS[1:]):
-                v = table[i, j]
-                row.append(str(int(v)) if col in LONG_COLUMNS else fmt(v))
-            w.writerow(row)
-    open(os.path.join(out_dir, "_SUCCESS"), "w").close()
+            w.writerow(_host_row(pth, table[i], fmt))
+    _end_part(out_dir)
     return part
+
+
+# Rows per cdr_csv_format call of write_spark_csv_device.  A call keeps, per
+# row of the 10-column table with paths of about 30 bytes: 80 B of table, 320 B
+# of cell slots (32 B each), 8 + 4 + 8 + 16 B of offsets, quoted lengths, byte
+# offsets and the deferred list, and the text bound 2 * 30 + 3 + 27 * 10 = 333 B
+# on the device and, pinned, on the host: about 770 B of device scratch and
+# 350 B of pinned memory per row.  2^18 rows bound them at about 200 MiB and
+# 90 MiB whatever the table's size (100M rows: 382 calls), while a call still
+# gives every CU of the device several workgroups.
+CSV_CHUNK_ROWS = 1 << 18
+
+
+class _Bytes:
+    """csv.writer target that collects UTF-8 bytes (newline="" semantics)."""
+
+    def __init__(self):
+        self.parts = []
+
+    def write(self, text):
+        self.parts.append(text.encode("utf-8"))
+
+
+def write_spark_csv_device(out_dir: str, paths, table, *, ctx: Context | None = None,
+                           chunk_rows: int | None = None) -> str:
+    """``write_spark_csv`` with the rows formatted on the device
+    (``Context.csv_format``, csrc/csvout.hip): the same directory layout and,
+    byte for byte, the same file as the host writer with the pre-19 digits
+    (``java_double_legacy``).  Rows the device defers (a value outside its
+    range, a NUL or CR in the path) are formatted by the host code and spliced
+    in, so the host writer's exceptions surface unchanged too.  One
+    ``csv_format`` call and one binary write per ``chunk_rows`` rows (default
+    ``CSV_CHUNK_ROWS``); the row text does not depend on the chunking.  Leaves
+    ``ctx.last_csv = {"rows", "deferred", "bytes"}`` (bytes: the file's)."""
+    ctx = ctx if ctx is not None else default_context()
+    chunk = CSV_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)
+    if chunk < 1:
+        raise ValueError("chunk_rows must be at least 1")
+    table = np.asarray(table, dtype=np.float64)
+    n = len(paths)
+    long_cols = [j for j, col in enumerate(OUT_COLUMNS[1:]) if col in LONG_COLUMNS]
+    out_dir, part = _begin_part(out_dir)
+    n_deferred = 0
+    with open(part, "wb") as fh:
+        fh.write((",".join(OUT_COLUMNS) + "\n").encode("utf-8"))
+        for lo in range(0, n, chunk):
+            hi = min(lo + chunk, n)
+            text, deferred = ctx.csv_format(table[lo:hi], paths[lo:hi], long_cols)
+            if len(deferred):
+                text = _splice_deferred(text, deferred, paths, table, lo)
+                n_deferred += len(deferred)
+            fh.write(memoryview(text))
+        size = fh.tell()
+    _end_part(out_dir)
+    ctx.last_csv = {"rows": n, "deferred": n_deferred, "bytes": size}
+    return part
+
+
+def _splice_deferred(text, deferred, paths, table, lo: int) -> bytes:
+    """The chunk's text with the host's rows at the deferred rows' offsets."""
+    sink = _Bytes()
+    w = csv.writer(sink, lineterminator="\n")
+    text = memoryview(text)
+    pos = 0
+    for row, off in deferred:
+        sink.parts.append(bytes(text[pos:off]))
+        pos = int(off)
+        w.writerow(_host_row(paths[lo + int(row)], table[lo + int(row)], java_double_legacy))
+    sink.parts.append(bytes(text[pos:]))
+    return b"".join(sink.parts)
+
+
+def _write_features(out_dir: str, paths, table, ctx: Context | None = None) -> str:
+    """The device writer for the pre-19 digits (the only ones it has); the host
+    writer for CDR_JAVA_DOUBLE=19 or CDR_CSV_HOST=1.  Same bytes either way."""
+    if _double_formatter() is java_double or os.environ.get("CDR_CSV_HOST") == "1":
+        return write_spark_csv(out_dir, paths, table)
+    return write_spark_csv_device(out_dir, paths, table, ctx=ctx)
 
 
 def main(argv=None):
@@ -492,13 +583,13 @@ def main(argv=None):
         paths, table = sharded_compute_features(args.manifest, args.access_log, ctx,
                                                 Comm(dist, torch.device("cuda", local)))
         if dist.get_rank() == 0:
-            write_spark_csv(args.out, paths, table)
+            _write_features(args.out, paths, table, ctx)
             print("Wrote features to", args.out)
         ctx.close()
         dist.destroy_process_group()
         return
     paths, table = compute_features(args.manifest, args.access_log)
-    write_spark_csv(args.out, paths, table)
+    _write_features(args.out, paths, table)
     print("Wrote features to", args.out)
 
 

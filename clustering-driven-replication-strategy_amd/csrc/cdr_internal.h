@@ -325,6 +325,14 @@ struct Ctx {
   // scatter kernels ms} (cdr_quality_timing)
   DevBuf q_buf;
   double q_ms[4] = {0.0, 0.0, 0.0, 0.0};
+  // csvout.hip: the table, the 32-byte cell slots, the paths (bytes, int64
+  // offsets), per row the quoted path length (-1 deferred) and the byte offset,
+  // the workgroup sums, the deferred list, the text; the pinned copy of the
+  // text and the list; {cell kernel, scan + emit, copies} ms of the last call
+  DevBuf csv_table, csv_slots, csv_pbytes, csv_poff, csv_qlen, csv_rowoff, csv_part, csv_def,
+      csv_out;
+  HostBuf csv_host;
+  double csv_ms[3] = {0.0, 0.0, 0.0};
   // clusters of the grouped rows (cdr_medians_group); 0 = none: whatever
   // replaces the points, rewrites the labels or reuses med_vals / med_off /
   // med_out (medians_segmented) clears it, and the pass entries refuse to run.

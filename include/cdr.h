@@ -513,6 +513,34 @@ int cdr_features_finalize(cdr_ctx* ctx, int64_t n_files, const int64_t* counts,
                           const double* creation_s, double observation_end,
                           double* out);
 
+/* ---- features CSV on the device: src/compute_features.py:96 ---- */
+/* The rows of the features CSV without the header: "path,cell,...,cell\n" per
+ * row of table (host, (n_rows, n_cols) row-major), 1 <= n_cols <= 16 (else
+ * CDR_ERR_UNSUPPORTED).  Bit j of long_mask prints column j as a long
+ * (Python's str(int(v))), the others as the pre-19 JDK's Double.toString
+ * (compute_features.java_double_legacy).  The paths are UTF-8 bytes + n_rows+1
+ * int64 offsets as in the manifest ingest; a path with ',', '"' or '\n' is wrapped
+ * in '"' with every '"' doubled, as csv.writer(lineterminator="\n") does.
+ *
+ * A row is deferred to the host when a double cell is a subnormal or a finite
+ * value outside 2^-128 <= |x| < 2^128, when a long cell is NaN, infinite or
+ * |v| >= 2^63, or when its path holds a NUL or CR byte.  It adds no bytes to
+ * out and is listed in deferred as the pair {row, byte offset in out where its
+ * text belongs}, in row order.  *written = bytes in out, *n_deferred = pairs.
+ * CDR_ERR_ARG, with nothing written to out or deferred, when cap or
+ * deferred_cap is below what the call needs (the bound below, and n_rows,
+ * always suffice).  n_rows == 0 writes nothing.  Runs on the context stream.
+ *
+ * The bound (host only): 2 * path_bytes_total + n_rows * (3 + 27 * n_cols).
+ * The timing entry: out[3] = {cell kernel ms, scan + emit kernels ms, copies ms}
+ * of the last format call.                                                    */
+int cdr_csv_format(cdr_ctx* ctx, int64_t n_rows, int32_t n_cols, uint32_t long_mask,
+                   const double* table, const char* path_bytes, const int64_t* path_off,
+                   char* out, int64_t cap, int64_t* written, int64_t* deferred,
+                   int64_t deferred_cap, int64_t* n_deferred);
+int cdr_csv_bound(int64_t n_rows, int32_t n_cols, int64_t path_bytes_total, int64_t* bytes);
+int cdr_csv_timing(cdr_ctx* ctx, double* out);
+
 /* ---- cluster quality (extension: no reference counterpart) ------------- */
 /* Validity indices of a clustering of the resident points, for choosing the
  * k the reference fixes (src/main.py --k).  The distance is the reference's
