@@ -143,6 +143,9 @@ SIGNATURES = {
                         _PI64], None),
     "cdr_csv_bound": ([_I64, _I32, _I64, _PI64], None),
     "cdr_csv_timing": ([_P, _P], None),
+    "cdr_csv_read": ([_P, _P, _I64, _I64, _I32, _P, _I32, _P, _P, _P, _I64], None),
+    "cdr_csv_read_finish": ([_P, _P, _P, _I64, _P], None),
+    "cdr_csv_read_timing": ([_P, _P], None),
     "cdr_host_seq_sum": ([_P, _I64, _F64], ctypes.c_double),
 }
 
@@ -1015,6 +1018,54 @@ class Context:
         """{cell kernel, scan + emit kernels, copies} ms of the last csv_format."""
         out = np.zeros(3, dtype=np.float64)
         _check(self._lib.cdr_csv_timing(self._h, _ptr(out)))
+        return out
+
+    # -- features CSV read on the device (csrc/csvin.hip) --------------------
+    def csv_read(self, data, body_off: int, n_cols: int, sel, deferred_cap: int = 1 << 20):
+        """First half of the device read (include/cdr.h cdr_csv_read): `data`
+        is the whole file (bytes-like), `sel` the file columns of the features.
+        Returns {"rows", "deferred_rows", "guard", "col_kinds" (d, 4) int64,
+        "deferred" (m, 3) int64 {row, byte begin, byte end}}; deferred holds
+        min(deferred_rows, deferred_cap) rows.  The points are not usable until
+        ``csv_read_finish``."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        d = int(sel.size)
+        status = np.zeros(3, dtype=np.int64)
+        kinds = np.zeros((max(d, 1), 4), dtype=np.int64)
+        cap = max(int(deferred_cap), 0)
+        deferred = np.empty((max(cap, 1), 3), dtype=np.int64)
+        self.restat_n = None
+        _check(self._lib.cdr_csv_read(self._h, _ptr(buf) if buf.size else None, buf.size,
+                                      int(body_off), int(n_cols), _ptr(sel), d, _ptr(status),
+                                      _ptr(kinds), _ptr(deferred), cap))
+        m = min(int(status[1]), cap)
+        return {"rows": int(status[0]), "deferred_rows": int(status[1]), "guard": int(status[2]),
+                "col_kinds": kinds[:d], "deferred": deferred[:m].copy()}
+
+    def csv_read_finish(self, rows, values, want_x: bool = True):
+        """Second half (cdr_csv_read_finish): the host-parsed `values` (m, d)
+        of the deferred `rows`; returns X (n, d) float64 when want_x.  A
+        non-finite value raises NanProbabilities as ``load_points`` does; the
+        X read so far is then in the exception's ``X`` attribute."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).ravel()
+        info = self.info()
+        n, d = info["n"], info["d"]
+        values = np.ascontiguousarray(values, dtype=np.float64).reshape(rows.size, d)
+        X = np.empty((n, d), dtype=np.float64) if want_x else None
+        try:
+            _check(self._lib.cdr_csv_read_finish(self._h, _ptr(rows) if rows.size else None,
+                                                 _ptr(values) if rows.size else None, rows.size,
+                                                 _ptr(X) if want_x else None))
+        except NanProbabilities as e:
+            e.X = X
+            raise
+        return X
+
+    def csv_read_timing(self) -> np.ndarray:
+        """{upload, record index, parse kernel, finish} ms of the last csv_read."""
+        out = np.zeros(4, dtype=np.float64)
+        _check(self._lib.cdr_csv_read_timing(self._h, _ptr(out)))
         return out
 
 

@@ -333,6 +333,16 @@ struct Ctx {
       csv_out;
   HostBuf csv_host;
   double csv_ms[3] = {0.0, 0.0, 0.0};
+  // csvin.hip: the file's body (zero-padded to a whole tile and one more), the
+  // tiles' scan elements and their prefix, the scan's partials, the per-lane
+  // terminator masks, the records' end indexes, scalars + kind counts, the
+  // parse blocks' deferred elements / prefix / masks, the parse workgroups'
+  // kind counters, the column map, the deferred list; cin_pending: cdr_csv_read
+  // ran and cdr_csv_read_finish has not; {upload, index, parse, finish} ms
+  DevBuf cin_bytes, cin_tile, cin_part, cin_mask, cin_ends, cin_sc, cin_blk, cin_cnt, cin_map,
+      cin_def;
+  bool cin_pending = false;
+  double cin_ms[4] = {0.0, 0.0, 0.0, 0.0};
   // clusters of the grouped rows (cdr_medians_group); 0 = none: whatever
   // replaces the points, rewrites the labels or reuses med_vals / med_off /
   // med_out (medians_segmented) clears it, and the pass entries refuse to run.
@@ -382,6 +392,12 @@ void points_analyze_and_store(Ctx& c, const double* host_X);
 void points_generate(Ctx& c, int64_t n_total, int64_t row_begin, int32_t n_blobs,
                      uint64_t seed);
 void points_finish_analysis(Ctx& c);
+// A producer that writes the F64 points on the device (csvin.hip): begin resets
+// the point state for (n, d) and leaves a zeroed planar x64 and no usable
+// points (mode 0); finish takes the statistics and decides the mode, exactly as
+// points_analyze_and_store ends.
+void points_begin_resident(Ctx& c, int64_t n, int32_t d);
+void points_finish_resident(Ctx& c);
 
 void lloyd_step_f32x(Ctx& c, const double* C, int32_t k, int64_t* out,
                      bool out_on_device);

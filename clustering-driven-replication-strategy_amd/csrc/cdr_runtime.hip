@@ -335,6 +335,7 @@ static void reset_points(Ctx& c, int64_t n, int32_t d) {
   c.zb_valid = false;
   c.ll_on = false;
   c.med_k = 0;
+  c.cin_pending = false;  // a csv read's half-written points are gone
   c.labels.ensure(sizeof(int32_t) * c.n_pad);
   HIP_CHECK(hipMemsetAsync(c.labels.p, 0, sizeof(int32_t) * c.n_pad, c.stream));
 }
@@ -357,6 +358,19 @@ void points_analyze_and_store(Ctx& c, const double* hX) {
   }
   HIP_CHECK(hipStreamSynchronize(c.stream));
   stage.release();
+  std::vector<unsigned long long> st;
+  run_stats(c, false, st);
+  decide_mode(c, st, true, c.n);
+}
+
+void points_begin_resident(Ctx& c, int64_t n, int32_t d) {
+  reset_points(c, n, d);
+  c.mode = 0;  // no usable points until points_finish_resident
+  c.x64.ensure(sizeof(double) * (size_t)d4_of(d) * c.n_pad);
+  HIP_CHECK(hipMemsetAsync(c.x64.p, 0, sizeof(double) * (size_t)d4_of(d) * c.n_pad, c.stream));
+}
+
+void points_finish_resident(Ctx& c) {
   std::vector<unsigned long long> st;
   run_stats(c, false, st);
   decide_mode(c, st, true, c.n);
@@ -457,7 +471,9 @@ int cdr_destroy(cdr_ctx* h) {
                     &c.f64x_T, &c.f64x_walk, &c.f64x_G, &c.f64x_GS, &c.f64x_GC, &c.f64x_prof, &c.f64x_E2, &c.f64x_ord, &c.f64x_dirty, &c.med_hist,
                     &c.fb_accum, &c.q_acc, &c.xs16, &c.xa32, &c.xb16, &c.big_sums, &c.big_chunks, &c.seed_near, &c.seed_cents, &c.seed_ccd, &c.seg_tails, &c.seg_ents, &c.seg_scan, &c.seg_items, &c.seg_meta, &c.seed_tail_plan, &c.seed_x16, &c.seed_e16, &c.seed_mu, &c.seed_run_buf, &c.mv_list, &c.lab8, &c.zb, &c.xh16, &c.bnd, &c.t_acc, &c.dmin32, &c.bs32, &c.cent32r, &c.mv_count, &c.ll_C, &c.ll_new, &c.ll_sums, &c.ll_ref,
                     &c.ll_state, &c.q_buf, &c.csv_table, &c.csv_slots, &c.csv_pbytes, &c.csv_poff,
-                    &c.csv_qlen, &c.csv_rowoff, &c.csv_part, &c.csv_def, &c.csv_out};
+                    &c.csv_qlen, &c.csv_rowoff, &c.csv_part, &c.csv_def, &c.csv_out,
+                    &c.cin_bytes, &c.cin_tile, &c.cin_part, &c.cin_mask, &c.cin_ends, &c.cin_sc,
+                    &c.cin_blk, &c.cin_cnt, &c.cin_map, &c.cin_def};
   for (DevBuf* b : bufs) b->release();
   c.h_small.release();
   c.h_up.release();

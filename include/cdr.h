@@ -541,6 +541,50 @@ int cdr_csv_format(cdr_ctx* ctx, int64_t n_rows, int32_t n_cols, uint32_t long_m
 int cdr_csv_bound(int64_t n_rows, int32_t n_cols, int64_t path_bytes_total, int64_t* bytes);
 int cdr_csv_timing(cdr_ctx* ctx, double* out);
 
+/* ---- features CSV read on the device: src/main.py:75-81 ---- */
+/* pd.read_csv(path)[CLUSTERING_FEATURES].values of the reference, into the
+ * resident points: the same float64 bits as pandas' default float parser gives
+ * (precise_xstrtod, which is not correctly rounded; csrc/csv_parse.h restates
+ * it), in two calls with the caller's host patch between them.
+ *
+ * cdr_csv_read: bytes[0, nbytes) is the whole file, body_off the offset of the
+ *   first byte after the header record (the caller parses the header), n_cols
+ *   the header's field count (1..32767), sel[d] the distinct file columns of
+ *   the d features (1 <= d <= 16, else CDR_ERR_UNSUPPORTED), in feature order.
+ *   Replaces the context's points: finds the records as pandas' tokenizer does
+ *   ('\n' outside quotes, a '\r' before it dropped, empty lines skipped, a
+ *   last line without '\n' kept), splits each and parses the selected cells
+ *   into the F64 point layout.  The points are not usable until the finish.
+ *   status[0] = rows, status[1] = deferred rows, status[2] = the file offset of
+ *   the first byte where a quote is not where pandas' quoting and plain quote
+ *   parity agree (an opening quote not at a field start, a closing quote not
+ *   followed by ',', '"', '\r', '\n' or the end, a file that ends inside
+ *   quotes) or where a line of blanks and tabs starts (pandas skips it); -1 if
+ *   none.  With status[2] >= 0 the rows are not pandas' rows: the caller takes
+ *   the whole file to the host.
+ *   col_kinds[4 j + t]: cells of feature j of kind t (0 int-like of at most 15
+ *   digits, 1 float, 2 empty = NaN, 3 deferred) over the rows with the header's
+ *   field count and no quote, NUL or lone CR.
+ *   A row is deferred when its field count differs from n_cols, when it holds
+ *   a '"', a NUL or a '\r' that is not before its '\n', or when a selected cell
+ *   is of kind 3 (csrc/csv_parse.h lists what that is; nothing is guessed).
+ *   deferred receives min(status[1], deferred_cap) triples {row, byte begin,
+ *   byte end} (file offsets, the terminator excluded) in row order.
+ * cdr_csv_read_finish: rows[m] with values (m, d) row-major overwrite the
+ *   deferred rows with what the host parsed; X_out, when not NULL, receives
+ *   the (n, d) row-major float64 matrix; then the point statistics and the
+ *   storage mode are taken exactly as cdr_points_load_f64 ends (CDR_ERR_NAN
+ *   for a non-finite value; X_out is complete by then).  CDR_ERR_STATE without
+ *   a cdr_csv_read before it.
+ * cdr_csv_read_timing: out[4] = {upload, record index, parse kernel, finish}
+ *   ms of the last read.                                                     */
+int cdr_csv_read(cdr_ctx* ctx, const char* bytes, int64_t nbytes, int64_t body_off,
+                 int32_t n_cols, const int32_t* sel, int32_t d, int64_t* status,
+                 int64_t* col_kinds, int64_t* deferred, int64_t deferred_cap);
+int cdr_csv_read_finish(cdr_ctx* ctx, const int64_t* rows, const double* values, int64_t m,
+                        double* X_out);
+int cdr_csv_read_timing(cdr_ctx* ctx, double* out);
+
 /* ---- cluster quality (extension: no reference counterpart) ------------- */
 /* Validity indices of a clustering of the resident points, for choosing the
  * k the reference fixes (src/main.py --k).  The distance is the reference's
