@@ -168,6 +168,12 @@ __device__ __forceinline__ int binade_e(double P) {
   frexp(P, &ex);  // P in [2^(ex-1), 2^ex)
   return ex - 1;
 }
+// A running value that has a binade: positive and finite.  frexp of inf
+// leaves no usable exponent (0 here) and (long long)ldexp(inf, .) no usable
+// grid count: once a sum had overflowed, f64_walk's integer state turned the
+// running inf into 2^63 2^-53 = 1024 after the group and went on adding to
+// that.  An inf (or nan) running value only ever takes real additions.
+__device__ __forceinline__ bool has_binade(double s) { return s > 0.0 && s < INFINITY; }
 // (GC: the clusters' member counts per group as well, from the waves of
 // feature 0 - f64_predict_b adds them up; null: not wanted)
 __global__ __launch_bounds__(256) void f64_predict_a(const double* __restrict__ A,
@@ -525,7 +531,7 @@ __global__ __launch_bounds__(256) void f64_walk(const S* __restrict__ X, int64_t
   // one block by transfer or element by element (wave-uniform b)
   auto step_block = [&](int64_t b, int e, int flags, long long d0, int dd) {
     bool ok = false;
-    if (!(flags & 4) && s > 0.0) {
+    if (!(flags & 4) && has_binade(s)) {
       int ex;
       frexp(s, &ex);
       if (ex - 1 == e && e >= kMinE) {
@@ -597,7 +603,7 @@ __global__ __launch_bounds__(256) void f64_walk(const S* __restrict__ X, int64_t
   long long sN = 0;
   auto to_int = [&]() {
     sE = kENone;
-    if (s > 0.0) {
+    if (has_binade(s)) {
       int ex;
       frexp(s, &ex);
       if (ex - 1 >= kMinE) {
@@ -690,7 +696,7 @@ __global__ __launch_bounds__(256) void f64_walk(const S* __restrict__ X, int64_t
         if (!rest) break;
         i = __builtin_amdgcn_readfirstlane(__ffsll((long long)rest) - 1);  // skip empty blocks
         int es = kENone;
-        if (s > 0.0) {
+        if (has_binade(s)) {
           int ex;
           frexp(s, &ex);
           if (ex - 1 >= kMinE) es = ex - 1;
@@ -1638,7 +1644,7 @@ __global__ __launch_bounds__(256) void f64s_compose(const F64Item* __restrict__ 
       const F64Item x = it[i];
       if (x.kind == kF64Run) {
         ok = false;
-        if (any && s > 0.0) {
+        if (any && has_binade(s)) {
           int ex;
           frexp(s, &ex);
           if (ex - 1 == x.e && x.e >= kMinE) {

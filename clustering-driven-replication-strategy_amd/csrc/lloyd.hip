@@ -1663,7 +1663,13 @@ void lloyd_step_f32r(Ctx& c, const float* C, int32_t k, double* sums, int64_t* c
                      c.labels.as<int32_t>(), c.n, k, reinterpret_cast<unsigned long long*>(cnt_pre));
   HIP_CHECK(hipGetLastError());
   if (!getenv("CDR_F64_SERIAL") && f32_sums_parallel(c, k, c.f64_sums.as<double>())) {
+    // the blocks f64_walk<float> re-added element by element, as the F64 step reports them
+    std::vector<long long> w((size_t)k * d);
+    HIP_CHECK(hipMemcpyAsync(w.data(), c.f64x_walk.p, sizeof(long long) * w.size(),
+                             hipMemcpyDeviceToHost, c.stream));
+    HIP_CHECK(hipStreamSynchronize(c.stream));
     c.f64x_walked = 0;
+    for (long long v : w) c.f64x_walked += v;
   } else {
     const int threads = k * d;
     if (c.mode == CDR_MODE_F32X)
