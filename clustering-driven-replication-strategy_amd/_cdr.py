@@ -94,6 +94,8 @@ SIGNATURES = {
     "cdr_f64s_chain": ([_P, _P], None),
     "cdr_profile_kernel": ([_P, _P, _I32], None),
     "cdr_lloyd_screen_layout": ([_P, _P], None),
+    "cdr_lloyd_watch_info": ([_P, _P], None),
+    "cdr_debug_watch": ([_P, _P, _I64, _P, _I64, _P, _P], None),
     "cdr_lloyd_big_layout": ([_P, _P], None),
     "cdr_debug_big_plan": ([_P, _I32, _P, _I64, _PI64], None),
     "cdr_points_sqdev": ([_P, _P, _PF64], None),
@@ -606,6 +608,29 @@ class Context:
         _check(self._lib.cdr_lloyd_screen_layout(self._h, _ptr(out)))
         names = ("workgroups", "slot_wg", "dyn_pct", "max_chunks", "nchunks", "word_bytes")
         return {nm: int(v) for nm, v in zip(names, out)}
+
+    def watch_info(self) -> dict:
+        """The 2-byte bounded screen's watch list after the last step
+        (cdr_lloyd_watch_info): mode -1 while the list path is off."""
+        out = np.zeros(12, dtype=np.int64)
+        _check(self._lib.cdr_lloyd_watch_info(self._h, _ptr(out)))
+        names = ("mode", "listed", "failed", "epochs", "full_steps", "list_steps", "waves",
+                 "range", "cap", "next_list", "carried", "n_pad")
+        return {nm: int(v) for nm, v in zip(names, out)}
+
+    def debug_watch(self) -> dict:
+        """Test hook (cdr_debug_watch): the bound words, the watch list's
+        per-wave regions and lengths, and the code tables T, H and the H of
+        the list's build."""
+        info = self.watch_info()
+        words = np.zeros(info["n_pad"], dtype=np.uint16)
+        entries = np.zeros((info["waves"], info["cap"]), dtype=np.uint32)
+        counts = np.zeros(info["waves"], dtype=np.int32)
+        tables = np.zeros((3, 64), dtype=np.uint32)
+        _check(self._lib.cdr_debug_watch(self._h, _ptr(words), words.size, _ptr(entries),
+                                         entries.size, _ptr(counts), _ptr(tables)))
+        return {"words": words, "entries": entries, "counts": counts, "T": tables[0],
+                "H": tables[1], "HL": tables[2], **info}
 
     def big_layout(self) -> dict:
         """What the last large-k step chose and counted (cdr_lloyd_big_layout);

@@ -101,7 +101,8 @@ constexpr int kPointGroup = 64;   // points per wave iteration in the screen
 // default path.  The switches the tests use to reach a tested alternative
 // (CDR_BOUNDS, CDR_NO_DELTA, CDR_S32B_SPLIT, CDR_S32BS_SPLIT, CDR_EXACT_ASSIGN,
 // CDR_F64_SERIAL, CDR_F64S_FORCE_CHAIN, CDR_GROUPBY_SORT, CDR_GB_BLOCK,
-// CDR_GB_BALLOT, CDR_GB_PASS3, CDR_S32BS_CUS, CDR_S32BS_DYN_MIN, CDR_QUALITY_BUDGET) are read with
+// CDR_GB_BALLOT, CDR_GB_PASS3, CDR_S32BS_CUS, CDR_S32BS_DYN_MIN, CDR_QUALITY_BUDGET,
+// CDR_S32BS_WATCH, CDR_S32BS_WATCH_MIN, CDR_S32BS_WATCH_BETA, CDR_S32BS_WATCH_CAP) are read with
 // getenv in both builds.
 inline const char* exp_env(const char* name) {
 #ifdef CDR_EXPERIMENTS
@@ -252,6 +253,13 @@ struct Ctx {
   // slot_wg, dyn_pct, bs_max_chunks, nchunks, word bytes; zeros: none yet
   int32_t s32_layout[6] = {0, 0, 0, 0, 0, 0};
   DevBuf zl, zn;  // split bounded screen: per-wave lists of failed points (screen32bz), lengths
+  // screen32bs16's watch list: per-wave regions of watch_cap
+  // entries, their lengths and the last screen's failed entries per wave; the
+  // geometry (waves, points per wave, entries per region) the list path was on
+  // with at the last bounded screen (watch_on), which the build slot uses
+  DevBuf wl, wn, wf;
+  bool watch_on = false;
+  int32_t watch_waves = 0, watch_range = 0, watch_cap = 0;
   bool zb_valid = false, xh_valid = false, bnd_ok = false;
   int zb_fmt = 0;  // bound words in zb: 16 (2-byte, screen32bs) or 32 bits
   int64_t ll_fin_count = 0;  // finalizes since lloyd_begin (2-byte rebase schedule)

@@ -55,6 +55,10 @@ struct FinArgs {
   // a rebase of the 2-byte words may be decided at this step (the host then
   // runs zh_rebase_kernel before the next screen; screen32b.hip)
   int rebase_ok;
+  // the watch list (plan32.h kBndH, kBndWatch): on for the
+  // next screen, and the budget factor beta of H
+  int watch_on;
+  double watch_beta;
   int abl;  // timing experiments only (0 in the product build)
   unsigned long long* tprof;  // (experiments build: phase timestamps, thread 0)
 };
@@ -131,6 +135,7 @@ __device__ __forceinline__ void fin32_body(const FinArgs& a, unsigned char* __re
   double c0[V], c1[V], r0[V], r1[V], mu0[V], mu1[V];
   bool whead[V];
   long long w_old[V], g_old[V];
+  unsigned hl_old[V];  // the watch list's thresholds (plan32.h kBndHL)
   unsigned char* const bb = reinterpret_cast<unsigned char*>(a.bnd);
 #pragma unroll
   for (int v = 0; v < V; ++v) {
@@ -144,6 +149,7 @@ __device__ __forceinline__ void fin32_body(const FinArgs& a, unsigned char* __re
     w_old[v] = whead[v] ? a.bnd[j[v]] : 0;
     // the 2-byte words' base (plan32.h kBnd*)
     g_old[v] = whead[v] ? reinterpret_cast<const long long*>(bb + kBndG)[j[v]] : 0;
+    hl_old[v] = whead[v] ? reinterpret_cast<const unsigned*>(bb + kBndHL)[j[v]] : 0u;
   }
   int hdr0 = 0, e0c = 0;
   if (a.bnd) {
@@ -352,6 +358,7 @@ __device__ __forceinline__ void fin32_body(const FinArgs& a, unsigned char* __re
       else if (hdr0 == 0) e0n = -20;
       e0n = e0n < -120 ? -120 : (e0n > 100 ? 100 : e0n);
     }
+    int past = 0;  // some T_j above the H_j the watch list was built with
 #pragma unroll
     for (int v = 0; v < V; ++v) {
       if (!whead[v]) continue;
@@ -360,19 +367,43 @@ __device__ __forceinline__ void fin32_body(const FinArgs& a, unsigned char* __re
       const long long g_new = rebase ? wn[v] : g_old[v];
       reinterpret_cast<long long*>(bb + kBndG)[jj] = g_new;
       // (the words are in the new base when the next screen tests them)
-      reinterpret_cast<unsigned*>(bb + kBndT)[jj] =
+      const unsigned tj =
           exact ? zb16_thr(f32_up(ldexp((double)(wn[v] - g_new), -40)), e0n) : 1022u;
+      reinterpret_cast<unsigned*>(bb + kBndT)[jj] = tj;
+      // the watch list's budget: T_j stays <= H_j while W_j grows by at most
+      // beta times this step's increment (H_j >= T_j: the same rounding of a
+      // value at least as large)
+      const double hv = ldexp((double)(wn[v] - g_new), -40) +
+                        a.watch_beta * ldexp((double)(wn[v] - w_old[v]), -40);
+      const unsigned hj = exact && hv < 0x1p120 ? zb16_thr(f32_up(hv), e0n) : 1022u;
+      reinterpret_cast<unsigned*>(bb + kBndH)[jj] = hj < tj ? tj : hj;
+      past |= tj > hl_old[v];
       reinterpret_cast<float*>(bb + kBndWdg)[jj] =
           exact ? f32_dn(ldexp((double)(wn[v] - g_new), -40)) : -1.0f;
       reinterpret_cast<float*>(bb + kBndDG)[jj] =
           rebase ? f32_up(ldexp((double)(g_new - g_old[v]), -40)) : 0.0f;
     }
+    // the next screen's mode: the list while it exists, was built in this
+    // base and exponent and covers every threshold; anything else streams
+    // every word, and the list is rebuilt at the next build slot
+    past = __syncthreads_or(past);
     if (t == 0) {
       int* hd = reinterpret_cast<int*>(bb + kBndHdr);
       hd[0] = 1;
       hd[1] = e0c;
       hd[2] = e0n;
       hd[3] = rebase ? 1 : 0;
+      int* wh = reinterpret_cast<int*>(bb + kBndWatch);
+      const int list = a.watch_on && wh[kWValid] && !wh[kWOvf] && !rebase && !past ? kWatchList
+                                                                                  : kWatchFull;
+      wh[kWMode] = list;
+      wh[kWFin] = list;
+      wh[kWValid] = list;
+      // (a list that does not fit is not tried again at every slot: a build
+      // streams every word, ~130 us at 100M points where the gated slot costs 4)
+      if (wh[kWOvf]) wh[kWHold] = 1;
+      if (rebase) wh[kWHold] = 0;
+      wh[kWOvf] = 0;
     }
   }
   FIN_TP(3);

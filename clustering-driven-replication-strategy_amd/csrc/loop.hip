@@ -449,6 +449,14 @@ FinArgs ll_fin_args(Ctx& c) {
   // 2-byte words: a rebase may be decided every kRebaseEvery-th finalize
   // (the first one sets the base), each followed by zh_rebase_kernel
   a.rebase_ok = c.ll_fin_count % kRebaseEvery == 0 ? 1 : 0;
+  // the watch list: on when the step's screen had it on
+  // (tests: CDR_S32BS_WATCH_BETA = the budget factor, read on every call)
+  a.watch_on = c.watch_on ? 1 : 0;
+  a.watch_beta = kS32WatchBeta;
+  if (const char* e = std::getenv("CDR_S32BS_WATCH_BETA")) {
+    const double v = std::atof(e);
+    if (v >= 0.0 && v <= 1024.0) a.watch_beta = v;
+  }
   a.abl = 0;
   a.tprof = nullptr;
 #ifdef CDR_EXPERIMENTS
@@ -603,6 +611,69 @@ int cdr_lloyd_resume(cdr_ctx* h, const double* C, int32_t add_steps, int32_t hos
   c.lab8_valid = false;
   c.zb_valid = false;
   c.big_valid = false;
+  CDR_CATCH
+}
+
+int cdr_lloyd_watch_info(cdr_ctx* h, int64_t out[12]) {
+  CDR_TRY
+  if (!h || !out) CDR_FAIL(CDR_ERR_ARG, "null argument");
+  Ctx& c = h->c;
+  for (int i = 0; i < 12; ++i) out[i] = 0;
+  out[0] = -1;
+  out[11] = c.n_pad;
+  if (!c.watch_on || !c.bnd.p) return CDR_OK;
+  HIP_CHECK(hipSetDevice(c.device));
+  HIP_CHECK(hipStreamSynchronize(c.stream));
+  int wh[16];
+  HIP_CHECK(hipMemcpy(wh, static_cast<unsigned char*>(c.bnd.p) + kBndWatch, sizeof(wh),
+                      hipMemcpyDeviceToHost));
+  std::vector<int32_t> wn((size_t)c.watch_waves), wf((size_t)c.watch_waves);
+  HIP_CHECK(hipMemcpy(wn.data(), c.wn.p, sizeof(int32_t) * wn.size(), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(wf.data(), c.wf.p, sizeof(int32_t) * wf.size(), hipMemcpyDeviceToHost));
+  const bool any = wh[kWListN] + wh[kWFullN] > 0;
+  out[0] = any ? wh[kWLast] : -1;
+  if (wh[kWEpochs] > 0)
+    for (int32_t v : wn) out[1] += v;
+  if (any)
+    for (int32_t v : wf) out[2] += v;
+  out[3] = wh[kWEpochs];
+  out[4] = wh[kWFullN];
+  out[5] = wh[kWListN];
+  out[6] = c.watch_waves;
+  out[7] = c.watch_range;
+  out[8] = c.watch_cap;
+  out[9] = wh[kWMode] == kWatchList && wh[kWOvf] == 0 ? 1 : 0;
+  out[10] = wh[kWCarried];
+  CDR_CATCH
+}
+
+int cdr_debug_watch(cdr_ctx* h, uint16_t* words, int64_t n_words, uint32_t* entries,
+                    int64_t n_entries, int32_t* counts, uint32_t* tables) {
+  CDR_TRY
+  if (!h) CDR_FAIL(CDR_ERR_ARG, "null ctx");
+  Ctx& c = h->c;
+  if (!c.watch_on || !c.zb_valid || c.zb_fmt != 16)
+    CDR_FAIL(CDR_ERR_STATE, "watch list: the list path is not on");
+  if ((words && n_words != c.n_pad) ||
+      (entries && n_entries != (int64_t)c.watch_waves * c.watch_cap))
+    CDR_FAIL(CDR_ERR_ARG, "watch list: buffer sizes differ from cdr_lloyd_watch_info's");
+  HIP_CHECK(hipSetDevice(c.device));
+  HIP_CHECK(hipStreamSynchronize(c.stream));
+  if (words)
+    HIP_CHECK(hipMemcpy(words, c.zb.p, sizeof(uint16_t) * (size_t)c.n_pad, hipMemcpyDeviceToHost));
+  if (entries)
+    HIP_CHECK(hipMemcpy(entries, c.wl.p,
+                        sizeof(uint32_t) * (size_t)c.watch_waves * (size_t)c.watch_cap,
+                        hipMemcpyDeviceToHost));
+  if (counts)
+    HIP_CHECK(hipMemcpy(counts, c.wn.p, sizeof(int32_t) * (size_t)c.watch_waves,
+                        hipMemcpyDeviceToHost));
+  if (tables) {
+    const unsigned char* bt = static_cast<const unsigned char*>(c.bnd.p);
+    HIP_CHECK(hipMemcpy(tables, bt + kBndT, 256, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(tables + 64, bt + kBndH, 256, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(tables + 128, bt + kBndHL, 256, hipMemcpyDeviceToHost));
+  }
   CDR_CATCH
 }
 

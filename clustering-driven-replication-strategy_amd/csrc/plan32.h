@@ -38,8 +38,41 @@ __host__ __device__ inline Plan32Layout plan32_layout(int MT, int k, int d) {
 //   wdg [64] f32 W_j - G_j (new base) rounded down, for the words written now
 //   dG [64] f32  G_j(new) - G_j(old) rounded up (0 unless this step rebases)
 //   hdr [4] int32: base set, E0 old, E0 new, rebase (zh_rebase_kernel: old -> new)
+//   H [64] u32   the watch list's budget thresholds of this step (base and
+//                exponent of T): the code, rounded up as T is, of
+//                (W_j - G_j) + beta (this step's increment of W_j), <= 1022
+//   HL [64] u32  the H the current watch list was built with (zh_watch_kernel)
+//   watch [16] int32 (kW*, below): the mode of the next screen and the list's state
 constexpr size_t kBndWup = 512, kBndWdn = 768, kBndG = 1024, kBndT = 1536, kBndWdg = 1792,
-                 kBndDG = 2048, kBndHdr = 2304, kBndBytes = 2320;
+                 kBndDG = 2048, kBndHdr = 2304, kBndH = 2320, kBndHL = 2576, kBndWatch = 2832,
+                 kBndBytes = 2896;
+
+// The watch list (screen32bs's WATCH form): per wave of the
+// screen's grid the compact list of the points of its contiguous range whose
+// code is <= H_label, entries offset_in_range << 16 | word.  While T_j <= HL_j
+// for every j (T grows between rebases) a point that is not listed passes its
+// test, so the screen streams the list alone.  watch words:
+enum : int {
+  kWMode = 0,    // the next screen: kWatchList | kWatchFull (finalize; LIST again by a build)
+  kWFin = 1,     // the finalize's own decision (a build slot rebuilds on FULL)
+  kWValid = 2,   // a list exists and every step since its build ran on it
+  kWOvf = 3,     // a region overflowed in the last build (folded into valid by the finalize)
+  kWHold = 4,    // a build overflowed: no further build until a rebase (new codes) or a reset
+  kWEpochs = 5,  // lists built
+  kWFullN = 6,   // screens that streamed every word while the list path was on
+  kWListN = 7,   // screens that streamed the list
+  kWLast = 8,    // the last screen's mode
+  kWCarried = 9, // lists built in the pass that carried a rebase
+};
+constexpr int kWatchFull = 0, kWatchList = 1;
+// the budget factor beta (CDR_S32BS_WATCH_BETA): of 4, 8, 16, 32 at config 3
+// the lowest ms_per_step (profiles/r08_watch_beta_sweep.txt); a larger beta
+// lengthens the epochs but lists more points
+constexpr double kS32WatchBeta = 16.0;
+// the list path is on from this many padded points (CDR_S32BS_WATCH_MIN) while
+// a wave's range fits the entries' 16-bit offset
+constexpr long long kS32WatchMinPts = 1LL << 22;
+constexpr int kS32WatchMaxRange = 1 << 16;
 
 // 2-byte bound words (screen32bs): code << 6 | label.  The
 // code is a truncated 10-bit float (4 exponent bits from 2^E0, 6 mantissa

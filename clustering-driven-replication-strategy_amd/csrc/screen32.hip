@@ -613,6 +613,10 @@ static void screen32_delta_step(Ctx& c, int QH, int MT, int k, const h8* dfrag,
     if (c.zb_fmt != zfmt) c.zb_valid = false;
     c.zb_fmt = zfmt;
     c.zb.ensure(sizeof(uint32_t) * (size_t)c.n_pad);
+    // the watch list belongs to the words: whatever resets
+    // them (the first bounded step, a host take-over, a resume, another word
+    // format) leaves no list
+    bool watch_reset = !c.zb_valid;
     if (!c.zb_valid) {
       bound_words_reset(z16, c.stream, c.lab8.as<uint8_t>(), c.zb.p, c.n, c.n_pad, gate);
       HIP_CHECK(hipGetLastError());
@@ -731,9 +735,59 @@ static void screen32_delta_step(Ctx& c, int QH, int MT, int k, const h8* dfrag,
       // the near-tie list holds at most the points of a wave's chunks
       // (the dynamic tail: twice the static share plus the two groups a
       // claiming wave may hold, so the waves' budgets cover the pool)
-      const int64_t need =
+      int64_t need =
           (b.dyn ? 2 * bs_max_chunks(b, nwg) + 2 * kBPD + 1 : bs_max_chunks(b, nwg)) *
           (z16 ? kZ16Chunk : kBChunk);
+      // The watch list: wave w of this grid keeps the points [w wrange,
+      // (w + 1) wrange) in a region of wcap entries.  On for 2-byte words from
+      // kS32WatchMinPts padded points (tests: CDR_S32BS_WATCH_MIN) while the
+      // range fits the entries' 16-bit offset; CDR_S32BS_WATCH=0: off.  The
+      // capacity is half the range: a longer list (4 bytes an entry) streams
+      // more bytes than the words (2 bytes a point), and the largest list of
+      // the beta sweep at config 3 stayed far below it (tests:
+      // CDR_S32BS_WATCH_CAP entries, up to the range).  All read on every call.
+      b.watch = nullptr;
+      b.wl = nullptr;
+      b.wn = b.wf = nullptr;
+      b.wcap = b.wrange = 0;
+      bool watch = z16 && !(b.dbg & 1);
+      if (const char* e = std::getenv("CDR_S32BS_WATCH")) watch = watch && std::atoi(e) != 0;
+      int64_t wmin = kS32WatchMinPts;
+      if (const char* e = std::getenv("CDR_S32BS_WATCH_MIN")) {
+        const long long v = std::atoll(e);
+        if (v >= 1) wmin = v;
+      }
+      const int64_t wrange = ceil_div(b.nchunks, (int64_t)nwaves) * kZ16Chunk;
+      watch = watch && c.n_pad >= wmin && wrange <= kS32WatchMaxRange;
+      if (watch) {
+        int64_t wcap = ceil_div(wrange / 2, (int64_t)256) * 256;
+        if (const char* e = std::getenv("CDR_S32BS_WATCH_CAP")) {
+          const long long v = std::atoll(e);
+          if (v >= 1) wcap = ceil_div(std::min<int64_t>(v, wrange), (int64_t)256) * 256;
+        }
+        if (!c.watch_on || c.watch_waves != nwaves || c.watch_range != wrange || c.watch_cap != wcap)
+          watch_reset = true;  // (a list of another geometry)
+        c.watch_waves = nwaves;
+        c.watch_range = (int32_t)wrange;
+        c.watch_cap = (int32_t)wcap;
+        c.wl.ensure(sizeof(uint32_t) * (size_t)nwaves * (size_t)wcap);
+        c.wn.ensure(sizeof(int32_t) * (size_t)nwaves);
+        c.wf.ensure(sizeof(int32_t) * (size_t)nwaves);
+        b.watch = reinterpret_cast<int*>(static_cast<unsigned char*>(c.bnd.p) + kBndWatch);
+        b.wl = c.wl.as<uint32_t>();
+        b.wn = c.wn.as<int32_t>();
+        b.wf = c.wf.as<int32_t>();
+        b.wcap = (int)wcap;
+        b.wrange = (int)wrange;
+        need = std::max(need, wrange);  // (the WATCH form's tail records: at most its entries)
+      } else if (c.watch_on) {
+        watch_reset = true;  // (this screen writes words the list does not see)
+      }
+      const bool was_on = c.watch_on;
+      c.watch_on = watch;
+      if (watch_reset && (watch || was_on))  // mode FULL, no list (kWMode .. kWHold)
+        HIP_CHECK(hipMemsetAsync(static_cast<unsigned char*>(c.bnd.p) + kBndWatch, 0,
+                                 5 * sizeof(int), c.stream));
       if (need > b.p.cap) {
         c.fb_list.ensure(sizeof(int2) * (size_t)nwaves * (size_t)need);
         b.p.fb_list = c.fb_list.as<int2>();
@@ -761,6 +815,8 @@ static void screen32_delta_step(Ctx& c, int QH, int MT, int k, const h8* dfrag,
         screen32bz_launch(grid, c.stream, b);
         if (prof) prof_mark_sub(c);
       }
+      // (the list path: both forms, each gated on the mode word; one exits at once)
+      if (b.watch) screen32bs_watch_launch(Q, MT, grid, c.stream, b);
       screen32bs_launch(Q, MT, grid, c.stream, b, split_env);
 #ifdef CDR_EXPERIMENTS
       if (tprof_on) s32bs_tprof_report(c, tprof_buf, nwaves, split_env);

@@ -204,6 +204,16 @@ struct S32BArgs {
   // each; the launch zeroes the other parity's counters for the next one)
   unsigned* dyn;
   int dyn_par, dyn_pct;
+  // the watch list (watch null: the list path is off): the
+  // watch words of Ctx::bnd (plan32.h kW*: the default form runs on
+  // kWatchFull, the WATCH form on kWatchList with no overflow), wave w's
+  // entries wl[w wcap .. + wn[w]) of the points [w wrange, (w + 1) wrange),
+  // and the failed entries per wave of the last screen
+  int* watch;
+  uint32_t* wl;
+  int32_t* wn;
+  int32_t* wf;
+  int wcap, wrange;
 };
 constexpr int kZ16Chunk = 512;  // points per wave-chunk of the 2-byte word stream (8 per lane)
 // the dynamic tail's static percent (100: off; 90: 3-5 us less per config-3
@@ -363,5 +373,7 @@ void zh_rebase(Ctx& c, const long long* gate);
 // screen32bs.hip: screen32bs<Q, MT, split> (split: the lists of screen32bz)
 int screen32bs_blocks_per_cu(int Q, int MT);
 void screen32bs_launch(int Q, int MT, dim3 grid, hipStream_t s, const S32BArgs& p, bool split);
+// ... and its WATCH form on the same grid (both gate on the mode word)
+void screen32bs_watch_launch(int Q, int MT, dim3 grid, hipStream_t s, const S32BArgs& p);
 
 }  // namespace cdr

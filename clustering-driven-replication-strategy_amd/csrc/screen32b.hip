@@ -2,7 +2,8 @@
 // loop; d <= 16, k <= 64: configs 2, 3): screen32b (LDS queue and fused fixup,
 // CDR_S32B_SPLIT=0), screen32bz (the word stream of the two-launch form,
 // CDR_S32BS_SPLIT=1, whose lists screen32bs.hip decides), and the kernels
-// that reset and rebase the bound words of either width.
+// that reset and rebase the bound words of either width and build the 2-byte
+// words' watch list (zh_watch_kernel).
 //
 // screen32p still reads every point's 32-byte hi copy every step.  After the
 // first steps almost every point keeps its label by a wide margin and the
@@ -551,10 +552,101 @@ __global__ __launch_bounds__(256) void zh_rebase_kernel(uint16_t* __restrict__ z
   }
 }
 
+// The build slot of the watch list, in zh_rebase_kernel's
+// place while the list path is on: a rebase carries the words as above, and
+// when the finalize rebased or chose kWatchFull (no list, its budget spent, an
+// overflow) the same pass over the words builds the list: wave w of the
+// screen's grid appends offset << 16 | word for every point of [w wrange,
+// (w + 1) wrange) with code <= H_label to its own region (no atomics) and
+// writes its count.  Code 0 is always listed, a padding row (1023 > H) never.
+// A region that overflows sets kWOvf: the screens then stream every word, and
+// no list is built again before the next rebase (kWHold).
+__global__ __launch_bounds__(256) void zh_watch_kernel(uint16_t* __restrict__ zh, int64_t n_pad,
+                                                       unsigned char* __restrict__ bt,
+                                                       const long long* __restrict__ gate,
+                                                       uint32_t* __restrict__ wl,
+                                                       int32_t* __restrict__ wn, int wcap,
+                                                       int wrange) {
+  if (gate && gate[0] == 0) return;
+  const int* hd = reinterpret_cast<const int*>(bt + kBndHdr);
+  int* wh = reinterpret_cast<int*>(bt + kBndWatch);
+  const bool reb = hd[3] != 0;
+  if (!reb && (wh[kWFin] == kWatchList || wh[kWHold])) return;  // the list stands, or none fits
+  __shared__ float dgs[64];
+  __shared__ unsigned hs[64];
+  const int t = threadIdx.x, lane = t & 63;
+  if (t < 64) {
+    dgs[t] = reinterpret_cast<const float*>(bt + kBndDG)[t];
+    hs[t] = reinterpret_cast<const unsigned*>(bt + kBndH)[t];
+  }
+  __syncthreads();
+  if (blockIdx.x == 0) {  // (the other workgroups read kWFin and kBndH only)
+    if (t < 64) reinterpret_cast<unsigned*>(bt + kBndHL)[t] = hs[t];
+    if (t == 0) {
+      wh[kWMode] = kWatchList;
+      wh[kWValid] = 1;
+      wh[kWEpochs] += 1;
+      if (reb) wh[kWCarried] += 1;
+    }
+  }
+  const int e0o = hd[1], e0n = hd[2];
+  typedef unsigned u4v __attribute__((ext_vector_type(4)));
+  const int wave = blockIdx.x * 4 + (t >> 6);
+  const int64_t p0 = (int64_t)wave * wrange;
+  const int64_t p1 = p0 + wrange < n_pad ? p0 + wrange : n_pad;
+  uint32_t* const out = wl + (size_t)wave * wcap;
+  int cnt = 0;
+  constexpr int kU = 4;  // chunks in flight
+  for (int64_t c0 = p0; c0 < p1; c0 += kU * kZ16Chunk) {
+    u4v z[kU];
+#pragma unroll
+    for (int i = 0; i < kU; ++i) {
+      const int64_t ci = c0 + i * kZ16Chunk < p1 ? c0 + i * kZ16Chunk : c0;  // (past the end: again)
+      z[i] = __builtin_nontemporal_load(reinterpret_cast<const u4v*>(zh + ci) + lane);
+    }
+#pragma unroll
+    for (int i = 0; i < kU; ++i) {
+      const int64_t ci = c0 + i * kZ16Chunk;
+      if (ci >= p1) break;
+      if (reb) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const unsigned lo = z[i][q] & 0xFFFFu, hi = z[i][q] >> 16;
+          z[i][q] = zb16_rebase(lo, dgs[lo & 63u], e0o, e0n) |
+                    zb16_rebase(hi, dgs[hi & 63u], e0o, e0n) << 16;
+        }
+        __builtin_nontemporal_store(z[i], reinterpret_cast<u4v*>(zh + ci) + lane);
+      }
+      const unsigned off = (unsigned)(ci - p0) + 8u * (unsigned)lane;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const unsigned w = (z[i][u >> 1] >> (16 * (u & 1))) & 0xFFFFu;
+        const bool listed = (w >> 6) <= hs[w & 63u];
+        const unsigned long long m = __ballot(listed);
+        if (m) {
+          const int r = cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32),
+                                                        __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+          if (listed && r < wcap) out[r] = (off + (unsigned)u) << 16 | w;
+          cnt += __popcll(m);
+        }
+      }
+    }
+  }
+  if (lane == 0) {
+    wn[wave] = cnt < wcap ? cnt : wcap;
+    if (cnt > wcap) wh[kWOvf] = 1;
+  }
+}
+
 void zh_rebase(Ctx& c, const long long* gate) {
   if (!c.zb_valid || c.zb_fmt != 16 || !c.bnd_ok) return;  // (no words to carry)
-  hipLaunchKernelGGL(zh_rebase_kernel, dim3(2048), dim3(256), 0, c.stream, c.zb.as<uint16_t>(),
-                     c.n_pad, reinterpret_cast<const unsigned char*>(c.bnd.p), gate);
+  if (c.watch_on)
+    hipLaunchKernelGGL(zh_watch_kernel, dim3(c.watch_waves / 4), dim3(256), 0, c.stream,
+                       c.zb.as<uint16_t>(), c.n_pad, static_cast<unsigned char*>(c.bnd.p), gate,
+                       c.wl.as<uint32_t>(), c.wn.as<int32_t>(), c.watch_cap, c.watch_range);
+  else
+    hipLaunchKernelGGL(zh_rebase_kernel, dim3(2048), dim3(256), 0, c.stream, c.zb.as<uint16_t>(),
+                       c.n_pad, reinterpret_cast<const unsigned char*>(c.bnd.p), gate);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -33,6 +33,11 @@
 // screen32bz's wave w and decodes its entries with the same chunk range); the
 // batches come from that list, entries two batches ahead and rows one batch
 // ahead of the decision.
+// WATCH (screen32bs<Q, MT, false, true>): phase 1 streams the
+// wave's watch list (zh_watch_kernel, screen32b.hip: the points whose word
+// could fail within the drift budget) instead of every bound word; the rest
+// is the default form's code, and a new word goes to the point's entry too.
+// Both forms are enqueued every step and gate on the mode word.
 #include "screen32_common.h"
 #include "screen32_fix.h"
 
@@ -57,8 +62,9 @@ constexpr int kDirectDense = CDR_S32BS_DENSE;
 // 6-12 clear
 constexpr unsigned kNotScreened = 0xFFFFFFC0u;
 
-template <int Q, int MT, bool SPLIT = false>
+template <int Q, int MT, bool SPLIT = false, bool WATCH = false>
 __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
+  static_assert(!(SPLIT && WATCH) && (!WATCH || CDR_S32BS_LAZY), "the WATCH form: 2-byte words, lazy phase 2");
   const S32PArgs& a = B.p;
   const FixArgs& F = a.fx;
 #ifdef CDR_EXPERIMENTS
@@ -81,6 +87,18 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
   if (!SPLIT && B.dyn && blockIdx.x == 0 && threadIdx.x < 32)
     B.dyn[((B.dyn_par ^ 1) * 32 + threadIdx.x) * 32] = 0u;
   if (a.gate && a.gate[0] == 0) return;
+  // the watch list's mode word: the WATCH form runs on
+  // kWatchList with no overflowed region, the default form otherwise
+  if constexpr (!SPLIT) {
+    if (B.watch) {
+      const bool list = B.watch[kWMode] == kWatchList && B.watch[kWOvf] == 0;
+      if (list != WATCH) return;
+      if (blockIdx.x == 0 && threadIdx.x == 0) {  // (cdr_lloyd_watch_info)
+        B.watch[WATCH ? kWListN : kWFullN] += 1;
+        B.watch[kWLast] = WATCH ? kWatchList : kWatchFull;
+      }
+    }
+  }
   typedef unsigned u4v __attribute__((ext_vector_type(4)));
   typedef float f2 __attribute__((ext_vector_type(2)));
   __shared__ __attribute__((aligned(16))) float c32s[64 * kPrStr + 128];
@@ -101,6 +119,11 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
   const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wv);
   const int64_t nchunks = B.nchunks;
   const int k = a.k, d = a.d, d1 = d + 1;
+  // the WATCH form: this wave's entries (offset << 16 | word) of the points
+  // from pbase on; the LDS list holds the failed entries and, kWL words on,
+  // their slots
+  uint32_t* const wlw = WATCH ? B.wl + (size_t)wave * B.wcap : nullptr;
+  const int pbase = WATCH ? wave * B.wrange : 0;
 
   // ---- phase 1 loads: 2-byte words, 8 per lane per 1 KiB chunk (the split
   // form: screen32bz streamed 4-byte words) ----
@@ -120,7 +143,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
   // the dynamic tail (B.dyn): this wave's static chunks end at swend, the
   // region's pool [P0, wend) goes out kBPD chunks at a time from dctr
   // (chunk indices: int, below 2^31 - the host's n_pad)
-  const bool dyn = !SPLIT && B.dyn != nullptr && B.slot_wg > 0;
+  const bool dyn = !SPLIT && !WATCH && B.dyn != nullptr && B.slot_wg > 0;
   // The pool is split over the 8 XCDs (workgroup b runs on XCD b % 8), one
   // counter each in its own 128-byte line: claims on one address serialise
   // (~10 ns apart, measured), so one counter per region holds the waves up
@@ -164,10 +187,17 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
     e0n = reinterpret_cast<const int*>(B.bt + kBndHdr)[2];
   }
   // a decided point's word (ok: bounds (l0, u0); w = __shfl(wnew_l, lab),
-  // taken by every lane) or "no bound"
-  auto zput = [&](int pt, bool ok, float l0, float u0, float w, unsigned lab) __attribute__((always_inline)) {
-    if constexpr (SPLIT) B.zb[pt] = ok ? zb_pack(l0, u0, w, lab) : (kZbStale | lab);
-    else B.zh[pt] = ok ? zb16_pack(l0, u0, w, e0n, lab) : (unsigned short)lab;
+  // taken by every lane) or "no bound"; the WATCH form writes it to the
+  // point's entry (slot sl) too: the two always agree, so the default form
+  // can take over at any step
+  auto zput = [&](int pt, int sl, bool ok, float l0, float u0, float w, unsigned lab) __attribute__((always_inline)) {
+    if constexpr (SPLIT) {
+      B.zb[pt] = ok ? zb_pack(l0, u0, w, lab) : (kZbStale | lab);
+    } else {
+      const unsigned short w16 = ok ? zb16_pack(l0, u0, w, e0n, lab) : (unsigned short)lab;
+      B.zh[pt] = w16;
+      if constexpr (WATCH) wlw[sl] = (unsigned)(pt - pbase) << 16 | w16;
+    }
   };
   const float msv = lane < d ? F.ms[lane] : 0.0f;        // lane f: -mu_f 2^sigma
   const float thr0 = a.thr_dev ? a.thr_dev[0] : a.thr0, thr_rel = a.thr_rel;
@@ -267,6 +297,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
   struct GB {
     f4 x[Q];  // the point's fp32 row
     int pt, ao;
+    int sl;  // (WATCH) the entry's slot
     bool valid;
   };
   // the split screen operands of the wave's 64 rows (lane l: point l): the
@@ -474,7 +505,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
   // one gathered batch: lane l decides point l
   auto decide = [&](const GB& g) __attribute__((always_inline)) {
     const bool valid = g.valid;
-    const int pt = g.pt, ao = g.ao;
+    const int pt = g.pt, ao = g.ao, sl = g.sl;
     float xh[DM];
     rowhat(g.x, xh);
     const float qa = q32(xh, ao);
@@ -522,7 +553,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
       const float l0 = fminf(lo, fmaf(nv[kPrH3 - 16], 1.0f - 0x1p-22f, -ua));
       const bool dec = !bad && l0 > ub * (1.0f + 0x1p-20f);
       const float w_b = __shfl(wnew_l, jb);
-      if (valid && dec) zput(pt, true, l0, ub, w_b, (unsigned)jb);
+      if (valid && dec) zput(pt, sl, true, l0, ub, w_b, (unsigned)jb);
       move(valid && dec, pt, ao, jb, g.x);
       need = valid && !dec;
     } else {
@@ -531,7 +562,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
       const float l0P = fmaf(hc[ao], 1.0f - 0x1p-22f, -uba);
       const bool keep = l0P > uba * (1.0f + 0x1p-20f);
       const float w_ao = __shfl(wnew_l, ao);
-      if (valid && keep) zput(pt, true, l0P, uba, w_ao, (unsigned)ao);
+      if (valid && keep) zput(pt, sl, true, l0P, uba, w_ao, (unsigned)ao);
       need = valid && !keep;
     }
     const unsigned long long nm = __ballot(need);
@@ -547,7 +578,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
         if (need) {
           const int r = __builtin_amdgcn_mbcnt_hi((unsigned)(nm >> 32),
                                                   __builtin_amdgcn_mbcnt_lo((unsigned)nm, 0u));
-          fb_region[fb_used + r] = int2{pt, (int)(kNotScreened | (unsigned)ao)};
+          fb_region[fb_used + r] = int2{WATCH ? sl : pt, (int)(kNotScreened | (unsigned)ao)};
         }
         // (readfirstlane: also keeps this update apart from the other counters',
         // which the compiler otherwise merges into one indexed stack slot)
@@ -569,7 +600,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
     if (need && cert) {
       float u0, l0;
       kcase(xx, vb, vs, u0, l0);
-      zput(pt, true, l0, u0, w_lab, (unsigned)label);
+      zput(pt, sl, true, l0, u0, w_lab, (unsigned)label);
     }
     const unsigned long long um = __ballot(unc);
     if constexpr (DEFER) {
@@ -581,7 +612,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
                                                 __builtin_amdgcn_mbcnt_lo((unsigned)um, 0u));
         // (the best key's label bits carry the old label: near_tie reads
         // the key's value only, and the tail needs no lab8 load)
-        fb_region[fb_used + r] = int2{pt, (int)((bA & ~63u) | (unsigned)ao)};
+        fb_region[fb_used + r] = int2{WATCH ? sl : pt, (int)((bA & ~63u) | (unsigned)ao)};
       }
       fb_used += __popcll(um);
     }
@@ -601,7 +632,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
       const float wl = __shfl(wnew_l, lab);
       if (unc) {
         labf = lab;
-        zput(pt, c2, l0, u0, wl, (unsigned)lab);
+        zput(pt, sl, c2, l0, u0, wl, (unsigned)lab);
       }
 #ifdef CDR_EXPERIMENTS
       } else if (unc) {
@@ -616,16 +647,30 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
 
   // ---- phase 2: the listed points, 64 per batch, two batches in flight ----
   unsigned* const fl = flist[wv];
-  auto gload = [&](GB& g, int b, int cnt) __attribute__((always_inline)) {
-    const int e = 64 * b + lane;
-    g.valid = e < cnt;
-    const unsigned ent = fl[g.valid ? e : 64 * b];  // (entry 64 b exists)
-    const int64_t ci = ebase + (int64_t)(ent >> SH) * estride;
-    const int64_t pt = ci * CH + ((ent >> 6) & (CH - 1));
+  constexpr int kWL = kSList / 2;             // (WATCH) entries the LDS list holds
+  constexpr int LS = WATCH ? kWL : kSList;    // ... of either form
+  constexpr int kRoom = WATCH ? 256 : CH;     // ... and one load's worth of them
+  // listed entry e: its point, old label (and slot), the row's loads
+  auto gfill = [&](GB& g, int e) __attribute__((always_inline)) {
+    const unsigned ent = fl[e];
+    int64_t pt;
+    if constexpr (WATCH) {
+      pt = pbase + (int)(ent >> 16);
+      g.sl = (int)fl[kWL + e];
+    } else {
+      const int64_t ci = ebase + (int64_t)(ent >> SH) * estride;
+      pt = ci * CH + ((ent >> 6) & (CH - 1));
+      g.sl = 0;
+    }
     g.pt = (int)pt;
     g.ao = (int)(ent & 63);
 #pragma unroll
     for (int q = 0; q < Q; ++q) g.x[q] = __builtin_nontemporal_load(XA4 + pt * Q + q);
+  };
+  auto gload = [&](GB& g, int b, int cnt) __attribute__((always_inline)) {
+    const int e = 64 * b + lane;
+    g.valid = e < cnt;
+    gfill(g, g.valid ? e : 64 * b);  // (entry 64 b exists)
   };
   auto phase2 = [&](int& cnt, bool last) __attribute__((always_inline)) {
     const int nb = last ? (cnt + 63) >> 6 : cnt >> 6;
@@ -687,6 +732,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
         const int64_t pt = ci * kBChunk + ((ent >> 6) & 255);
         g.pt = (int)pt;
         g.ao = (int)(ent & 63);
+        g.sl = 0;
 #pragma unroll
         for (int q = 0; q < Q; ++q) g.x[q] = __builtin_nontemporal_load(XA4 + pt * Q + q);
       };
@@ -722,7 +768,6 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
   // (returns with room for one more chunk's entries: the stream breaks its
   // group early when a chunk would not fit, which only dense failures do)
   auto step2 = [&](int& cnt, bool last) __attribute__((always_inline)) {
-    constexpr int kRoom = CH;
     for (;;) {
       if (pend) {
 #ifdef CDR_EXPERIMENTS
@@ -743,31 +788,29 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
       if (avail >= 64 || (last && avail > 0)) {
         const int e = head + lane;
         cur.valid = e < cnt;
-        const unsigned ent = fl[cur.valid ? e : head];
-        const int64_t ci = ebase + (int64_t)(ent >> SH) * estride;
-        const int64_t pt = ci * CH + ((ent >> 6) & (CH - 1));
-        cur.pt = (int)pt;
-        cur.ao = (int)(ent & 63);
-#pragma unroll
-        for (int q = 0; q < Q; ++q) cur.x[q] = __builtin_nontemporal_load(XA4 + pt * Q + q);
+        gfill(cur, cur.valid ? e : head);
         const int take = avail < 64 ? avail : 64;
         head = __builtin_amdgcn_readfirstlane(head + take);
         ttot += take;
         pend = true;
       }
-      if (head > 0 && !last && cnt + kRoom > kSList) {  // compact [head, cnt) to the front
+      if (head > 0 && !last && cnt + kRoom > LS) {  // compact [head, cnt) to the front
         const int m = cnt - head;
         for (int o = 0; o < m; o += 64) {  // (writes stay below the reads still to come)
           const int e2 = o + lane;
           const unsigned v = e2 < m ? fl[head + e2] : 0u;
+          unsigned vs = 0u;
+          if constexpr (WATCH) vs = e2 < m ? fl[kWL + head + e2] : 0u;
           __builtin_amdgcn_wave_barrier();
           if (e2 < m) fl[e2] = v;
+          if constexpr (WATCH)
+            if (e2 < m) fl[kWL + e2] = vs;
           __builtin_amdgcn_wave_barrier();
         }
         cnt = m;
         head = 0;
       }
-      const bool again = last ? (pend || cnt > head) : (cnt - head + kRoom > kSList);
+      const bool again = last ? (pend || cnt > head) : (cnt - head + kRoom > LS);
       if (!again) break;
     }
   };
@@ -775,6 +818,65 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
   constexpr int head = 0;  // (phase 2 in bursts compacts the list itself)
 #endif
 
+  if constexpr (WATCH) {
+  // ---- phase 1, the WATCH form: this wave's entries, 4 per lane per 16-byte
+  // load, kBPD loads issued together and phase 2 between the groups, as
+  // below.  An entry fails as its point's word does (code <= T_label); its
+  // copy and its slot go on the LDS list.  A load whose entries might not fit
+  // the list is left for the next group, which step2 makes room for.
+  const u4v* const wl4 = reinterpret_cast<const u4v*>(wlw);
+  const int total = __builtin_amdgcn_readfirstlane(B.wn[wave]);
+  const int ng = (total + 255) >> 8;
+  int cnt = 0;
+  auto insertw = [&](const u4v& z, int gi) __attribute__((always_inline)) {
+    const int e0 = 256 * gi + 4 * lane;
+    unsigned fm = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const unsigned w = z[u] & 0xFFFFu;
+      fm |= (unsigned)(e0 + u < total && (w >> 6) <= tls[w & 63u]) << u;
+    }
+    if (__ballot(fm != 0u)) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const bool fail = (fm >> u) & 1u;
+        const unsigned long long m = __ballot(fail);
+        if (m) {
+          if (fail) {
+            const int r = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32),
+                                                    __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            fl[cnt + r] = z[u];
+            fl[kWL + cnt + r] = (unsigned)(e0 + u);
+          }
+          cnt = __builtin_amdgcn_readfirstlane(cnt + __popcll(m));
+        }
+      }
+    }
+  };
+  int g0 = 0;
+  for (bool first = true;; first = false) {
+    const bool more = g0 < ng;  // (wave-uniform)
+    if (!first) step2(cnt, !more);
+    if (!more) break;
+#pragma unroll
+    for (int i = 0; i < kBPD; ++i) {
+      zc[i] = wl4[(size_t)(g0 + i < ng ? g0 + i : ng - 1) * 64 + lane];
+      __builtin_amdgcn_sched_barrier(0);  // (issued in order)
+    }
+    int adv = 0;
+#pragma unroll
+    for (int i = 0; i < kBPD; ++i) {
+      // insertw writes at the absolute index cnt, so the room is counted from
+      // there, not from head: step2 returns with cnt + kRoom <= LS (it compacts
+      // whenever head > 0 and that fails), so the group's first load always
+      // fits, and a later one that might not waits for the next group
+      if (g0 + i >= ng || cnt + kRoom > LS) break;
+      insertw(zc[i], g0 + i);
+      adv = i + 1;
+    }
+    g0 += adv;
+  }
+  } else {
   // ---- phase 1: the bound words, 8 points per lane per chunk ----
   // Groups of kBPD chunks issued together, phase 2 between groups.  The waits
   // must stay exact: vmcnt counts stores too and is in order, so a store or a
@@ -906,6 +1008,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
   }
 #undef gS
 #undef budget
+  }  // (!WATCH)
   }  // (!SPLIT)
   // ---- the uncertified points: the same split screen again (the same values),
   // every centroid whose key is within the threshold of the best is a
@@ -919,7 +1022,9 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
   if constexpr (DEFER) {
   // the next batch's records and rows load while one is decided
   // (Q >= 3: the records only - the rows ahead too spill registers)
-  constexpr int QA = Q < 3 ? Q : 0;
+  // (the WATCH form's records carry the entry's slot: the point comes from
+  // the entry, whose offset never changes, and the rows after it)
+  constexpr int QA = Q < 3 && !WATCH ? Q : 0;
   auto tload = [&](int e0, int2& rec, f4 (&xr)[Q]) __attribute__((always_inline)) {
     const int e = e0 + lane;
     rec = fb_region[e < fb_used ? e : e0];
@@ -936,10 +1041,14 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
     f4 xr[Q];
 #pragma unroll
     for (int q = 0; q < QA; ++q) xr[q] = xr_n[q];
+    int pt = rec.x, sl = 0;
+    if constexpr (WATCH) {
+      sl = rec.x;
+      pt = pbase + (int)(wlw[sl] >> 16);
+    }
 #pragma unroll
-    for (int q = QA; q < Q; ++q) xr[q] = XA4[(int64_t)rec.x * Q + q];
+    for (int q = QA; q < Q; ++q) xr[q] = XA4[(int64_t)pt * Q + q];
     if (e0 + 64 < fb_used) tload(e0 + 64, rec_n, xr_n);
-    const int pt = rec.x;
     const int ao = rec.y & 63;  // (the record's: unchanged until this pass decides the point)
     float xh[DM];
     rowhat(xr, xh);
@@ -965,7 +1074,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
         float u0, l0;
         kcase(xx, vb, vs, u0, l0);
         lab = (int)(bA & 63u);
-        zput(pt, true, l0, u0, w_c, (unsigned)lab);
+        zput(pt, sl, true, l0, u0, w_c, (unsigned)lab);
         tie = false;
       }
       fb_cert += __popcll(__ballot(cert));
@@ -978,7 +1087,7 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
       const float w_lab = __shfl(wnew_l, lt);
       if (tie) {
         lab = lt;
-        zput(pt, c2, l0, u0, w_lab, (unsigned)lab);  // the direct bounds, or none
+        zput(pt, sl, c2, l0, u0, w_lab, (unsigned)lab);  // the direct bounds, or none
       }
     }
     move(live, pt, ao, lab, xr);
@@ -990,6 +1099,8 @@ __global__ __launch_bounds__(256, 4) void screen32bs(S32BArgs B) {
     a.mv_count[wave] = mv_used;
     if (a.q_acc) a.q_acc[wave] += qtot;
     if (B.t_acc) B.t_acc[wave] += ttot;
+    if constexpr (!SPLIT)
+      if (B.wf) B.wf[wave] = ttot;  // (cdr_lloyd_watch_info: the entries or words that failed)
   }
   // this workgroup's moves into one run_sums slice (nothing to do: no atomics)
   if (__syncthreads_or(mv_used)) {
@@ -1024,6 +1135,13 @@ void screen32bs_launch(int Q, int MT, dim3 grid, hipStream_t s, const S32BArgs& 
     constexpr int Q_ = decltype(q)::value, MT_ = decltype(m)::value;
     if (split) hipLaunchKernelGGL((screen32bs<Q_, MT_, true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((screen32bs<Q_, MT_>), grid, dim3(256), 0, s, p);
+  });
+}
+
+void screen32bs_watch_launch(int Q, int MT, dim3 grid, hipStream_t s, const S32BArgs& p) {
+  dispatch_q_mt<4>(Q, MT, [&](auto q, auto m) {
+    hipLaunchKernelGGL((screen32bs<decltype(q)::value, decltype(m)::value, false, true>), grid,
+                       dim3(256), 0, s, p);
   });
 }
 

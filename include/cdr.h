@@ -341,6 +341,25 @@ int cdr_profile_kernel(cdr_ctx* ctx, char* buf, int32_t len);
  * statically, chunks, bytes per bound word (2 or 4)}; all zeros when no
  * bounded screen has run on the context.                                    */
 int cdr_lloyd_screen_layout(cdr_ctx* ctx, int32_t out[6]);
+/* The watch list of the 2-byte bounded screen after the context's last step
+ * (tests; synchronises the stream): out = {mode of the last
+ * screen (1: it streamed the list, 0: every word, -1: the list path is off or
+ * no screen has run with it), entries listed by the last build, entries (mode
+ * 1) or words (mode 0) that failed in the last screen, lists built, screens
+ * that streamed every word while the list path was on, screens that streamed
+ * the list, waves, points per wave, entries a wave's region holds, 1 when the
+ * next screen would stream the list, lists built in the pass that carried a
+ * rebase of the words, padded points (the bound words the context keeps)}.   */
+int cdr_lloyd_watch_info(cdr_ctx* ctx, int64_t out[12]);
+/* Test hook: the n_words bound words (2 bytes each), the watch list's
+ * n_entries region entries (waves x entries per region,
+ * offset_in_wave_range << 16 | word), the regions' lengths (waves) and the
+ * code tables T | H | H of the list's build (3 x 64); any pointer may be
+ * null.  An error while the list path is off, or when n_words or n_entries
+ * differ from the padded points or waves x entries per region that
+ * cdr_lloyd_watch_info reports.                                              */
+int cdr_debug_watch(cdr_ctx* ctx, uint16_t* words, int64_t n_words, uint32_t* entries,
+                    int64_t n_entries, int32_t* counts, uint32_t* tables);
 /* What the context's last large-k step (screen_big.hip) chose and counted
  * (tests): out = {DQ = ceil(d/16), KB = ceil(k/32), FG (features per update
  * pass), JB (key bits holding the centroid index), L1 threads (512 or 768),
