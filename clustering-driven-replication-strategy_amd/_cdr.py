@@ -127,6 +127,12 @@ SIGNATURES = {
     "cdr_medians_pass_hist": ([_P, _I32, _P], None),
     "cdr_medians_pass_select": ([_P, _I32, _P], None),
     "cdr_medians_finish": ([_P, _P], None),
+    "cdr_medians_global": ([_P, _P], None),
+    "cdr_medians_global_begin": ([_P, _I64, ctypes.POINTER(ctypes.c_int32), _PI64], None),
+    "cdr_medians_global_pass_hist": ([_P, _I32, _P], None),
+    "cdr_medians_global_pass_select": ([_P, _I32, _P], None),
+    "cdr_medians_global_finish": ([_P, _P], None),
+    "cdr_medians_global_timing": ([_P, _P], None),
     "cdr_features_exchange_pack": ([_P, _I32, _P, _P, _P, _PI64], None),
     "cdr_features_exchange_unpack": ([_P, _P, _I64, _I64, _I64], None),
     "cdr_features_load_events": ([_P, _I64, _P, _P, _P, _P, _I64, _P], None),
@@ -791,6 +797,45 @@ class Context:
         out = np.empty((self._med_k, self.info()["d"]), dtype=np.float64)
         _check(self._lib.cdr_medians_finish(self._h, _ptr(out)))
         return out
+
+    # -- medians of all points (src/main.py:31-38: global_medians) --------
+    def medians_global(self) -> np.ndarray:
+        """np.median of every feature over the resident points, (d,) float64
+        (cdr_medians_global)."""
+        out = np.empty(self.info()["d"], dtype=np.float64)
+        _check(self._lib.cdr_medians_global(self._h, _ptr(out)))
+        return out
+
+    def medians_global_begin(self, n_total: int):
+        """(passes, histogram words) for points sharded over ranks: n_total is
+        the row count of all shards."""
+        passes = ctypes.c_int32()
+        words = _I64()
+        _check(self._lib.cdr_medians_global_begin(self._h, int(n_total), ctypes.byref(passes),
+                                                  ctypes.byref(words)))
+        return int(passes.value), int(words.value)
+
+    def medians_global_pass_hist(self, p: int, hist) -> None:
+        """hist: a uint32 host array or a device pointer (int)."""
+        _check(self._lib.cdr_medians_global_pass_hist(
+            self._h, int(p), hist if isinstance(hist, int) else _ptr(hist)))
+
+    def medians_global_pass_select(self, p: int, hist) -> None:
+        _check(self._lib.cdr_medians_global_pass_select(
+            self._h, int(p), hist if isinstance(hist, int) else _ptr(hist)))
+
+    def medians_global_finish(self) -> np.ndarray:
+        out = np.empty(self.info()["d"], dtype=np.float64)
+        _check(self._lib.cdr_medians_global_finish(self._h, _ptr(out)))
+        return out
+
+    def medians_global_timing(self) -> dict:
+        """Histogram kernel times of the last medians_global call
+        (cdr_medians_global_timing)."""
+        out = np.zeros(11, dtype=np.float64)
+        _check(self._lib.cdr_medians_global_timing(self._h, _ptr(out)))
+        return {"hist_ms": float(out[0]), "hist_max_ms": float(out[1]), "passes": int(out[2]),
+                "pass_ms": [float(v) for v in out[3:3 + int(out[2])]]}
 
     # -- cluster quality (csrc/quality.hip) -------------------------------
     def silhouette(self, k: int, idx=None, labels=None):

@@ -810,3 +810,46 @@ def sharded_medians(ctx, comm: Comm, k: int) -> np.ndarray:
         ctx.medians_pass_select(p, handle)
     return ctx.medians_finish()
 
+
+def sharded_global_medians(ctx, comm: Comm) -> np.ndarray:
+    """Per-feature medians of all points (the scoring's global_medians,
+    src/main.py:31-38; np.median of each column as src/scoring.py:50-54 takes
+    it) of points sharded over the ranks: one SUM all-reduce of the row
+    counts, then per radix pass one SUM all-reduce of the d x 2 x 256 digit
+    histogram (RCCL on the device buffer under NCCL).  No labels are needed.
+    Every rank returns the same (d,) array, equal to np.median of the union."""
+    if comm.world == 1:
+        return ctx.medians_global()  # the same passes, histograms never leave the device
+    # as in sharded_medians: the storage mode sets the number of passes and the
+    # key space, so ranks that disagree all raise here, before any pass
+    info = ctx.info()
+    mode = np.array([info["mode"]], dtype=np.int64)
+    lo, hi = comm.allreduce_i64(mode, "min"), comm.allreduce_i64(mode, "max")
+    if int(lo[0]) != int(hi[0]):
+        raise RuntimeError("sharded_global_medians: the ranks' points are stored in different "
+                           f"modes (min {int(lo[0])}, max {int(hi[0])}); bring them to one "
+                           "with cdr_dist.unify_points first")
+    n_local = np.array([info["n"]], dtype=np.int64)
+    n_total = int(comm.allreduce_i64(n_local, "sum")[0])
+    passes, words = ctx.medians_global_begin(n_total)
+    if comm.device is not None and comm.dist:
+        import torch
+
+        buf = torch.empty(words, dtype=torch.int32, device=comm.device)
+        handle = buf.data_ptr()
+    else:
+        buf = np.zeros(words, dtype=np.uint32)
+        handle = buf
+    for p in range(passes):
+        ctx.medians_global_pass_hist(p, handle)
+        if comm.dist:
+            if comm.device is not None:
+                comm.fenced(ctx, comm.dist.all_reduce, buf)
+            else:
+                import torch
+
+                t = torch.from_numpy(buf.view(np.int32))
+                comm.dist.all_reduce(t)
+        ctx.medians_global_pass_select(p, handle)
+    return ctx.medians_global_finish()
+

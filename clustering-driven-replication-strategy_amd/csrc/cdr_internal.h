@@ -102,7 +102,7 @@ constexpr int kPointGroup = 64;   // points per wave iteration in the screen
 // (CDR_BOUNDS, CDR_NO_DELTA, CDR_S32B_SPLIT, CDR_S32BS_SPLIT, CDR_EXACT_ASSIGN,
 // CDR_F64_SERIAL, CDR_F64S_FORCE_CHAIN, CDR_GROUPBY_SORT, CDR_GB_BLOCK,
 // CDR_GB_BALLOT, CDR_GB_PASS3, CDR_S32BS_CUS, CDR_S32BS_DYN_MIN, CDR_QUALITY_BUDGET,
-// CDR_S32BS_WATCH, CDR_S32BS_WATCH_MIN, CDR_S32BS_WATCH_BETA, CDR_S32BS_WATCH_CAP) are read with
+// CDR_S32BS_WATCH, CDR_S32BS_WATCH_MIN, CDR_S32BS_WATCH_BETA, CDR_S32BS_WATCH_CAP, CDR_GMED_GRID) are read with
 // getenv in both builds.
 inline const char* exp_env(const char* name) {
 #ifdef CDR_EXPERIMENTS
@@ -357,6 +357,15 @@ struct Ctx {
   // med_begun: cdr_medians_begin has sized and filled med_out for this grouping
   int32_t med_k = 0;
   bool med_begun = false;
+  // medians of all points (cdr_medians_global*): buffers of their own, the row
+  // count + prefixes + ranks + result, and the [d][2][256] digit table.
+  // gmed_begun: cdr_medians_global_begin ran on the current points (whatever
+  // replaces or restats them clears it; the labels do not matter).  gmed_ms:
+  // {histogram launches ms, the longest, passes, then each pass's ms} of the last
+  // cdr_medians_global
+  DevBuf gmed_state, gmed_hist;
+  bool gmed_begun = false;
+  double gmed_ms[11] = {0.0};
   // timestamp range of the resident events (min, max, any null), computed by
   // the producer that wrote them (events_ts_range, groupby.hip); valid for
   // ev_tsr_n events until another writer of ev_ts clears ev_tsr_valid

@@ -299,6 +299,7 @@ static void decide_mode(Ctx& c, const std::vector<unsigned long long>& st,
   }
   c.have_labels = false;
   c.med_k = 0;  // (load, generate and restat all end here) the grouped rows are of other points
+  c.gmed_begun = false;  // and so are the global medians' prefixes
   c.run_valid = false;
   c.lab8_valid = false;
   c.zb_valid = false;
@@ -335,6 +336,7 @@ static void reset_points(Ctx& c, int64_t n, int32_t d) {
   c.zb_valid = false;
   c.ll_on = false;
   c.med_k = 0;
+  c.gmed_begun = false;
   c.cin_pending = false;  // a csv read's half-written points are gone
   c.labels.ensure(sizeof(int32_t) * c.n_pad);
   HIP_CHECK(hipMemsetAsync(c.labels.p, 0, sizeof(int32_t) * c.n_pad, c.stream));
@@ -469,6 +471,7 @@ int cdr_destroy(cdr_ctx* h) {
                     &c.gb_p1, &c.gb_p2, &c.gb_hist2, &c.gb_list, &c.gb_slots, &c.sim_cnt, &c.sim_off,
                     &c.sim_tmp, &c.sim_ms, &c.sim_mbase, &c.x_small, &c.x_buf, &c.x_prim, &c.f64x_A, &c.f64x_cnt, &c.f64x_E,
                     &c.f64x_T, &c.f64x_walk, &c.f64x_G, &c.f64x_GS, &c.f64x_GC, &c.f64x_prof, &c.f64x_E2, &c.f64x_ord, &c.f64x_dirty, &c.med_hist,
+                    &c.gmed_state, &c.gmed_hist,
                     &c.fb_accum, &c.q_acc, &c.xs16, &c.xa32, &c.xb16, &c.big_sums, &c.big_chunks, &c.seed_near, &c.seed_cents, &c.seed_ccd, &c.seg_tails, &c.seg_ents, &c.seg_scan, &c.seg_items, &c.seg_meta, &c.seed_tail_plan, &c.seed_x16, &c.seed_e16, &c.seed_mu, &c.seed_run_buf, &c.mv_list, &c.lab8, &c.zb, &c.xh16, &c.bnd, &c.t_acc, &c.dmin32, &c.bs32, &c.cent32r, &c.mv_count, &c.ll_C, &c.ll_new, &c.ll_sums, &c.ll_ref,
                     &c.ll_state, &c.q_buf, &c.csv_table, &c.csv_slots, &c.csv_pbytes, &c.csv_poff,
                     &c.csv_qlen, &c.csv_rowoff, &c.csv_part, &c.csv_def, &c.csv_out,

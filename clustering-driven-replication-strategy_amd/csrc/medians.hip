@@ -572,11 +572,375 @@ void medians_by_label(Ctx& c, int32_t k, double* out) {
   medians_finish(c, out);
 }
 
+// ---- medians of all resident points (main.py:31-38: global_medians) --------
+// The same radix select as the label medians with one "cluster" that holds
+// every row, so nothing is grouped or copied: each pass streams the resident
+// layout itself (x32 quad SoA, x64 planar) on a full grid and counts, per
+// feature, the digit of the values that still match each rank's prefix.  The
+// counters of a workgroup live in LDS ([kGmFeat][2][256] u32, 32 KiB: up to
+// five workgroups per CU); the non-zero ones are added to the global
+// [d][2][256] table with integer atomics at the end, so the result does not
+// depend on the order.  mg_begin / mg_select / mg_finish run with k = 1 and
+// the global row count.
+//
+// A wave's lanes always count the same feature, so its 64 LDS adds differ in
+// the digit alone, and in the first passes (and in every pass of a constant
+// column) nearly all of them name one counter: 64 adds on one address
+// serialise.  gm_add therefore peels digit groups off the wave: the first
+// active lane's digit is broadcast, a ballot counts the active lanes that
+// share it, and that lane adds the count once.  It goes on while the groups
+// are large (>= kGmPeel lanes) and leaves the rest to per-lane adds: one
+// round and one add per value on a constant column; on random digits one
+// round per batch of loads (the probe below), then per-lane adds, few of
+// which share a counter.
+constexpr int kGmFeat = 16;    // features per histogram workgroup (4 quads)
+constexpr int kGmThreads = 256;
+constexpr int kGmU = 8;        // 16-byte loads in flight per lane
+constexpr int kGmRows = 512;   // rows per wave turn: 64 kGmU (x32), 128 (kGmU / 2) (x64)
+constexpr int kGmPeel = 8;     // smallest digit group worth another peel round
+constexpr int kGmWgPerCu = 4;
+
+// hot (wave-uniform, one per feature and rank in the caller): the last probe
+// found a large group.  A probe value (the first of each batch of loads)
+// always peels; the others only while hot, so random digits pay one peel
+// round per batch and not per value.
+__device__ __forceinline__ void gm_add(unsigned* __restrict__ hb, unsigned dg, bool act,
+                                       int lane, bool probe, bool& hot) {
+  unsigned long long rem = __ballot(act);
+  if (probe || hot) {
+    bool first = true;
+    hot = false;
+    while (rem) {
+      const int lead = __ffsll((long long)rem) - 1;
+      const unsigned g = (unsigned)__builtin_amdgcn_readlane((int)dg, lead);
+      const unsigned long long m = __ballot(act && dg == g);
+      const int c = __popcll(m);
+      if (lane == lead) atomicAdd(&hb[g], (unsigned)c);
+      rem &= ~m;
+      if (first) hot = c >= kGmPeel;
+      first = false;
+      if (c < kGmPeel) break;
+    }
+  }
+  if ((rem >> lane) & 1ull) atomicAdd(&hb[dg], 1u);
+}
+
+// one value of feature slot fl (prefixes p0, p1) into the LDS table
+template <typename V>
+__device__ __forceinline__ void gm_count(unsigned* __restrict__ h, int fl, V v, bool live,
+                                         typename KeyOf<V>::K p0, typename KeyOf<V>::K p1,
+                                         typename KeyOf<V>::K mask, int sh, int lane, bool probe,
+                                         bool& hot0, bool& hot1) {
+  typedef typename KeyOf<V>::K K;
+  const K key = KeyOf<V>::key(v);
+  const unsigned dg = (unsigned)((key >> sh) & 0xFF);
+  const K top = key & mask;
+  gm_add(h + fl * 512, dg, live && top == p0, lane, probe, hot0);
+  if (p1 != p0)  // uniform branch
+    gm_add(h + fl * 512 + 256, dg, live && top == p1, lane, probe, hot1);
+}
+
+// F32X points.  blockIdx.y = chunk of kGmFeat features (nq quads of it real);
+// the waves of the grid take (512-row group, quad) items with a grid stride.
+__global__ __launch_bounds__(kGmThreads) void gm_hist32(const float* __restrict__ X, int64_t n,
+                                                        int64_t n_pad, int d,
+                                                        const unsigned long long* __restrict__ pref,
+                                                        int sh, unsigned* __restrict__ H) {
+  __shared__ unsigned h[kGmFeat * 512];
+  __shared__ unsigned sp[kGmFeat][2];
+  const int f0 = blockIdx.y * kGmFeat;
+  const int nfc = min(kGmFeat, d - f0);
+  const int nq = (nfc + 3) >> 2;
+  for (int i = threadIdx.x; i < kGmFeat * 512; i += kGmThreads) h[i] = 0;
+  for (int i = threadIdx.x; i < 2 * nfc; i += kGmThreads)
+    sp[i >> 1][i & 1] = (unsigned)pref[(int64_t)f0 * 2 + i];
+  __syncthreads();
+  const unsigned mask = sh + 8 >= 32 ? 0u : (~0u << (sh + 8));
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  constexpr int kW = kGmThreads / 64;
+  const int64_t groups = (n + kGmRows - 1) / kGmRows;
+  const int64_t items = groups * nq;
+  const float4* __restrict__ X4 = reinterpret_cast<const float4*>(X);
+  for (int64_t it = (int64_t)blockIdx.x * kW + w; it < items; it += (int64_t)gridDim.x * kW) {
+    const int64_t g = it / nq;
+    const int q = (int)(it - g * nq);
+    const int64_t r0 = g * kGmRows + lane;  // rows r0 + 64 u < n_pad (a multiple of kGmRows)
+    const float4* __restrict__ src = X4 + (int64_t)((f0 >> 2) + q) * n_pad + r0;
+    float4 v[kGmU];
+#pragma unroll
+    for (int u = 0; u < kGmU; ++u) v[u] = src[u * 64];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int fl = q * 4 + c;
+      if (fl >= nfc) break;  // the zero features that pad d to d4
+      const unsigned p0 = sp[fl][0], p1 = sp[fl][1];
+      bool hot0 = false, hot1 = false;
+#pragma unroll
+      for (int u = 0; u < kGmU; ++u) {
+        const float x = c == 0 ? v[u].x : c == 1 ? v[u].y : c == 2 ? v[u].z : v[u].w;
+        gm_count<float>(h, fl, x, r0 + u * 64 < n, p0, p1, mask, sh, lane, u == 0, hot0, hot1);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nfc * 512; i += kGmThreads) {
+    const unsigned cnt = h[i];
+    if (cnt) atomicAdd(&H[(int64_t)f0 * 512 + i], cnt);
+  }
+}
+
+// F64 points (planar): items are (512-row group, feature); a lane loads two
+// consecutive rows of the feature per 16-byte load.
+__global__ __launch_bounds__(kGmThreads) void gm_hist64(const double* __restrict__ X, int64_t n,
+                                                        int64_t n_pad, int d,
+                                                        const unsigned long long* __restrict__ pref,
+                                                        int sh, unsigned* __restrict__ H) {
+  __shared__ unsigned h[kGmFeat * 512];
+  __shared__ unsigned long long sp[kGmFeat][2];
+  const int f0 = blockIdx.y * kGmFeat;
+  const int nfc = min(kGmFeat, d - f0);
+  for (int i = threadIdx.x; i < kGmFeat * 512; i += kGmThreads) h[i] = 0;
+  for (int i = threadIdx.x; i < 2 * nfc; i += kGmThreads) sp[i >> 1][i & 1] = pref[(int64_t)f0 * 2 + i];
+  __syncthreads();
+  const unsigned long long mask = sh + 8 >= 64 ? 0ull : (~0ull << (sh + 8));
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  constexpr int kW = kGmThreads / 64;
+  constexpr int kU2 = kGmU / 2;
+  const int64_t groups = (n + kGmRows - 1) / kGmRows;
+  const int64_t items = groups * nfc;
+  for (int64_t it = (int64_t)blockIdx.x * kW + w; it < items; it += (int64_t)gridDim.x * kW) {
+    const int64_t g = it / nfc;
+    const int fl = (int)(it - g * nfc);
+    const int64_t r0 = g * kGmRows + 2 * lane;  // rows r0 + 128 u + {0, 1} < n_pad
+    const double2* __restrict__ src =
+        reinterpret_cast<const double2*>(X + (int64_t)(f0 + fl) * n_pad + r0);
+    double2 v[kU2];
+#pragma unroll
+    for (int u = 0; u < kU2; ++u) v[u] = src[u * 64];
+    const unsigned long long p0 = sp[fl][0], p1 = sp[fl][1];
+    bool hot0 = false, hot1 = false;
+#pragma unroll
+    for (int u = 0; u < kU2; ++u) {
+      const int64_t r = r0 + u * 128;
+      gm_count<double>(h, fl, v[u].x, r < n, p0, p1, mask, sh, lane, u == 0, hot0, hot1);
+      gm_count<double>(h, fl, v[u].y, r + 1 < n, p0, p1, mask, sh, lane, false, hot0, hot1);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nfc * 512; i += kGmThreads) {
+    const unsigned cnt = h[i];
+    if (cnt) atomicAdd(&H[(int64_t)f0 * 512 + i], cnt);
+  }
+}
+
+int lloyd_num_cus(int device);
+
+static void gm_need_points(const Ctx& c) {
+  if (c.mode != CDR_MODE_F32X && c.mode != CDR_MODE_F64)
+    CDR_FAIL(CDR_ERR_STATE, "global medians: no points loaded");
+  if (c.n >= (1ll << 32))
+    CDR_FAIL(CDR_ERR_UNSUPPORTED, "global medians: 2^32 points or more per shard");
+}
+
+static void gm_need_begun(const Ctx& c) {
+  gm_need_points(c);
+  if (!c.gmed_begun)
+    CDR_FAIL(CDR_ERR_STATE,
+             "global medians: no pass state of the current points: call "
+             "cdr_medians_global_begin first");
+}
+
+// gmed_state: the global row count, then pref[2d], rank[2d], out[d]
+static unsigned long long* gm_pref(const Ctx& c) {
+  return reinterpret_cast<unsigned long long*>(c.gmed_state.as<long long>() + 1);
+}
+static long long* gm_rank(const Ctx& c) {
+  return reinterpret_cast<long long*>(gm_pref(c) + 2 * (size_t)c.d);
+}
+
+int medians_global_begin(Ctx& c, int64_t n_total) {
+  gm_need_points(c);
+  c.gmed_begun = false;
+  if (n_total < c.n) CDR_FAIL(CDR_ERR_ARG, "global medians: n_total below the local row count");
+  if (n_total >= (1ll << 32))
+    CDR_FAIL(CDR_ERR_UNSUPPORTED, "global medians: 2^32 points or more");
+  const size_t d = (size_t)c.d;
+  c.gmed_state.ensure(sizeof(long long) * (1 + 2 * d + 2 * d) + sizeof(double) * d);
+  c.gmed_hist.ensure(sizeof(unsigned) * 512 * d);
+  long long* gcnt = c.gmed_state.as<long long>();
+  const long long nt = n_total;
+  HIP_CHECK(hipMemcpyAsync(gcnt, &nt, sizeof(long long), hipMemcpyHostToDevice, c.stream));
+  HIP_CHECK(hipStreamSynchronize(c.stream));  // nt is a stack variable
+  hipLaunchKernelGGL(mg_begin, dim3(ceil_div((int64_t)d, 256)), dim3(256), 0, c.stream, gcnt,
+                     c.d, 1, gm_pref(c), gm_rank(c));
+  HIP_CHECK(hipGetLastError());
+  c.gmed_begun = true;
+  return mg_passes(c);
+}
+
+// The histogram launch alone (the table zeroed first), for both entry forms.
+static void gm_launch_hist(Ctx& c, int pass) {
+  const int d = c.d, P = mg_passes(c);
+  const int sh = (P - 1 - pass) * 8;
+  unsigned* H = c.gmed_hist.as<unsigned>();
+  HIP_CHECK(hipMemsetAsync(H, 0, sizeof(unsigned) * 512 * (size_t)d, c.stream));
+  if (c.n <= 0) return;
+  const bool f32 = c.mode == CDR_MODE_F32X;
+  const int chunks = (int)ceil_div(d, kGmFeat);
+  // items of the fullest chunk, four waves per workgroup
+  const int per = std::min(d, kGmFeat);
+  const int64_t items = ceil_div(c.n, kGmRows) * (f32 ? (per + 3) / 4 : per);
+  int64_t gx = std::max<int64_t>(1, (int64_t)lloyd_num_cus(c.device) * kGmWgPerCu / chunks);
+  gx = std::min<int64_t>(gx, ceil_div(items, kGmThreads / 64));
+  // (CDR_GMED_GRID: fewer workgroups per chunk, for tests of the grid stride at small n)
+  if (const char* e = std::getenv("CDR_GMED_GRID"))
+    gx = std::min<int64_t>(gx, std::max<int64_t>(1, std::atoll(e)));
+  const dim3 grid((unsigned)gx, (unsigned)chunks);
+  if (f32)
+    hipLaunchKernelGGL(gm_hist32, grid, dim3(kGmThreads), 0, c.stream, c.x32.as<float>(), c.n,
+                       c.n_pad, d, gm_pref(c), sh, H);
+  else
+    hipLaunchKernelGGL(gm_hist64, grid, dim3(kGmThreads), 0, c.stream, c.x64.as<double>(), c.n,
+                       c.n_pad, d, gm_pref(c), sh, H);
+  HIP_CHECK(hipGetLastError());
+}
+
+static void gm_launch_select(Ctx& c, int pass) {
+  const int d = c.d, P = mg_passes(c);
+  const int sh = (P - 1 - pass) * 8;
+  const long long* gcnt = c.gmed_state.as<long long>();
+  if (c.mode == CDR_MODE_F32X)
+    hipLaunchKernelGGL(mg_select<float>, dim3(ceil_div(d, 256)), dim3(256), 0, c.stream,
+                       c.gmed_hist.as<unsigned>(), d, 1, gcnt, sh, gm_pref(c), gm_rank(c));
+  else
+    hipLaunchKernelGGL(mg_select<double>, dim3(ceil_div(d, 256)), dim3(256), 0, c.stream,
+                       c.gmed_hist.as<unsigned>(), d, 1, gcnt, sh, gm_pref(c), gm_rank(c));
+  HIP_CHECK(hipGetLastError());
+}
+
+static void gm_check_pass(const Ctx& c, int pass) {
+  gm_need_begun(c);
+  if (pass < 0 || pass >= mg_passes(c)) CDR_FAIL(CDR_ERR_ARG, "global medians: pass out of range");
+}
+
+void medians_global_pass_hist(Ctx& c, int pass, void* hist) {
+  gm_check_pass(c, pass);
+  gm_launch_hist(c, pass);
+  HIP_CHECK(hipMemcpyAsync(hist, c.gmed_hist.p, sizeof(unsigned) * 512 * (size_t)c.d,
+                           hipMemcpyDefault, c.stream));
+  HIP_CHECK(hipStreamSynchronize(c.stream));
+}
+
+void medians_global_pass_select(Ctx& c, int pass, const void* hist) {
+  gm_check_pass(c, pass);
+  HIP_CHECK(hipMemcpyAsync(c.gmed_hist.p, hist, sizeof(unsigned) * 512 * (size_t)c.d,
+                           hipMemcpyDefault, c.stream));
+  gm_launch_select(c, pass);
+}
+
+void medians_global_finish(Ctx& c, double* out) {
+  gm_need_begun(c);
+  const int d = c.d;
+  const long long* gcnt = c.gmed_state.as<long long>();
+  double* res = reinterpret_cast<double*>(gm_rank(c) + 2 * (size_t)d);
+  if (c.mode == CDR_MODE_F32X)
+    hipLaunchKernelGGL(mg_finish<float>, dim3(ceil_div(d, 256)), dim3(256), 0, c.stream, gcnt, d,
+                       1, gm_pref(c), res);
+  else
+    hipLaunchKernelGGL(mg_finish<double>, dim3(ceil_div(d, 256)), dim3(256), 0, c.stream, gcnt, d,
+                       1, gm_pref(c), res);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(out, res, sizeof(double) * d, hipMemcpyDeviceToHost, c.stream));
+  HIP_CHECK(hipStreamSynchronize(c.stream));
+}
+
+// One shard: every pass enqueued back to back, one wait at the end.  The
+// histogram launches are bracketed by events (cdr_medians_global_timing).
+void medians_global(Ctx& c, double* out) {
+  const int P = medians_global_begin(c, c.n);
+  std::vector<hipEvent_t> ev(2 * (size_t)P, nullptr);
+  for (hipEvent_t& e : ev) HIP_CHECK(hipEventCreate(&e));
+  try {
+    for (int p = 0; p < P; ++p) {
+      HIP_CHECK(hipEventRecord(ev[2 * p], c.stream));
+      gm_launch_hist(c, p);
+      HIP_CHECK(hipEventRecord(ev[2 * p + 1], c.stream));
+      gm_launch_select(c, p);
+    }
+    medians_global_finish(c, out);
+    double total = 0.0, longest = 0.0;
+    for (int p = 0; p < 8; ++p) c.gmed_ms[3 + p] = 0.0;
+    for (int p = 0; p < P; ++p) {
+      float ms = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&ms, ev[2 * p], ev[2 * p + 1]));
+      total += ms;
+      longest = std::max(longest, (double)ms);
+      c.gmed_ms[3 + p] = ms;
+    }
+    c.gmed_ms[0] = total;
+    c.gmed_ms[1] = longest;
+    c.gmed_ms[2] = (double)P;
+  } catch (...) {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    throw;
+  }
+  for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+}
+
 }  // namespace cdr
 
 using namespace cdr;
 
 extern "C" {
+
+/* ---- medians of all points: src/main.py:31-38, src/scoring.py:50-54 ---- */
+int cdr_medians_global(cdr_ctx* h, double* out) {
+  CDR_TRY
+  if (!h || !out) CDR_FAIL(CDR_ERR_ARG, "null argument");
+  HIP_CHECK(hipSetDevice(h->c.device));
+  medians_global(h->c, out);
+  CDR_CATCH
+}
+
+int cdr_medians_global_begin(cdr_ctx* h, int64_t n_total, int32_t* passes, int64_t* hist_words) {
+  CDR_TRY
+  if (!h || !passes || !hist_words) CDR_FAIL(CDR_ERR_ARG, "null argument");
+  HIP_CHECK(hipSetDevice(h->c.device));
+  *passes = medians_global_begin(h->c, n_total);
+  *hist_words = (int64_t)h->c.d * 512;
+  CDR_CATCH
+}
+
+int cdr_medians_global_pass_hist(cdr_ctx* h, int32_t pass, void* hist) {
+  CDR_TRY
+  if (!h || !hist) CDR_FAIL(CDR_ERR_ARG, "null argument");
+  HIP_CHECK(hipSetDevice(h->c.device));
+  medians_global_pass_hist(h->c, pass, hist);
+  CDR_CATCH
+}
+
+int cdr_medians_global_pass_select(cdr_ctx* h, int32_t pass, const void* hist) {
+  CDR_TRY
+  if (!h || !hist) CDR_FAIL(CDR_ERR_ARG, "null argument");
+  HIP_CHECK(hipSetDevice(h->c.device));
+  medians_global_pass_select(h->c, pass, hist);
+  CDR_CATCH
+}
+
+int cdr_medians_global_finish(cdr_ctx* h, double* out) {
+  CDR_TRY
+  if (!h || !out) CDR_FAIL(CDR_ERR_ARG, "null argument");
+  HIP_CHECK(hipSetDevice(h->c.device));
+  medians_global_finish(h->c, out);
+  CDR_CATCH
+}
+
+int cdr_medians_global_timing(cdr_ctx* h, double* out) {
+  CDR_TRY
+  if (!h || !out) CDR_FAIL(CDR_ERR_ARG, "null argument");
+  for (int i = 0; i < 11; ++i) out[i] = h->c.gmed_ms[i];
+  CDR_CATCH
+}
 
 int cdr_medians_segmented(cdr_ctx* h, const double* values, const int64_t* offsets,
                           int64_t n_segments, double* out) {

@@ -32,12 +32,33 @@ from _cdr import Context, default_context
 
 CATEGORIES = ("Hot", "Shared", "Moderate", "Archival")
 
-__all__ = ["ClusterClassifier", "CATEGORIES", "demo"]
+__all__ = ["ClusterClassifier", "CATEGORIES", "demo", "global_medians"]
 
 
 def _warn_empty_median() -> None:
     warnings.warn("Mean of empty slice.", RuntimeWarning, stacklevel=4)
     warnings.warn("invalid value encountered in scalar divide", RuntimeWarning, stacklevel=4)
+
+
+def global_medians(feature_names, *, context: Context | None = None, comm=None):
+    """{feature: np.float64 median over all files} of the points resident on
+    ``context`` (default: the process context ``kmeans`` used), in
+    ``feature_names`` order: the ``global_medians`` the classifier scores
+    against, which src/main.py:31-38 leaves as 0.5 placeholders.  Each value
+    is np.median of the column, computed on the device
+    (``Context.medians_global``); with ``comm`` over several ranks, each
+    holding a shard, the medians are those of the whole point set
+    (cdr_dist.sharded_global_medians)."""
+    ctx = context if context is not None else default_context()
+    if ctx.info()["d"] != len(feature_names):
+        raise ValueError("feature_names must name every column of X")
+    if comm is not None and comm.world > 1:
+        from cdr_dist import sharded_global_medians
+
+        med = sharded_global_medians(ctx, comm)
+    else:
+        med = ctx.medians_global()
+    return {name: np.float64(v) for name, v in zip(feature_names, med)}
 
 
 class ClusterClassifier:
@@ -56,6 +77,14 @@ class ClusterClassifier:
         self.directions = directions
         self.replication_factors = replication_factors
         self._context = context
+
+    @classmethod
+    def from_points(cls, weights, directions, replication_factors, feature_names, *,
+                    context: Context | None = None, comm=None):
+        """The classifier whose ``global_medians`` are the medians of the
+        resident points (``global_medians`` above) instead of placeholders."""
+        med = global_medians(feature_names, context=context, comm=comm)
+        return cls(med, weights, directions, replication_factors, context=context)
 
     def _ctx(self) -> Context:
         return self._context if self._context is not None else default_context()

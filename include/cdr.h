@@ -419,6 +419,39 @@ int cdr_medians_pass_hist(cdr_ctx* ctx, int32_t pass, void* hist);
 int cdr_medians_pass_select(cdr_ctx* ctx, int32_t pass, const void* hist);
 int cdr_medians_finish(cdr_ctx* ctx, double* out);
 
+/* ---- medians of all points: src/main.py:31-38 (global_medians) ---------- */
+/* out[f] = np.median of feature f over the resident points (the float64
+ * conversions of F32X points), exactly what compute_cluster_medians
+ * (src/scoring.py:50-54) returns for one cluster holding every file: the
+ * scoring's global_medians, which src/main.py:31-38 leaves as placeholders.
+ * An MSB radix select over the resident layout itself: no labels, no grouped
+ * copy, the histograms stay on the device.  Never -0.0; n = 0 gives NaN.    */
+int cdr_medians_global(cdr_ctx* ctx, double* out /* [d] */);
+/* The same in steps for points sharded over ranks (src/main.py:31-38,
+ * src/scoring.py:50-54): after a SUM all-reduce of the local row counts,
+ * cdr_medians_global_begin takes the global count and returns the number of
+ * radix passes (4 for F32X points, 8 for F64) and the histogram size in
+ * uint32 words (d * 512: [d][2 ranks][256]); per pass,
+ * cdr_medians_global_pass_hist writes this shard's digit counts to `hist`
+ * (host or device memory), the caller SUM-all-reduces them and
+ * cdr_medians_global_pass_select consumes the global counts;
+ * cdr_medians_global_finish writes out[d].  The calls keep buffers of their
+ * own: labels, grouped rows (cdr_medians_group) and the Lloyd state stay as
+ * they are, and a Lloyd step does not disturb them.  Loading, generating or
+ * restat'ing points ends the begun state: _pass_hist / _pass_select / _finish
+ * then fail with CDR_ERR_STATE until cdr_medians_global_begin has run again.
+ * CDR_ERR_STATE without points; CDR_ERR_UNSUPPORTED for 2^32 rows or more
+ * (in n_total or in the shard: the counters are uint32).                    */
+int cdr_medians_global_begin(cdr_ctx* ctx, int64_t n_total, int32_t* passes,
+                             int64_t* hist_words);
+int cdr_medians_global_pass_hist(cdr_ctx* ctx, int32_t pass, void* hist);
+int cdr_medians_global_pass_select(cdr_ctx* ctx, int32_t pass, const void* hist);
+int cdr_medians_global_finish(cdr_ctx* ctx, double* out);
+/* out[11] = {histogram kernels ms, the longest of them ms, passes, then the ms
+ * of pass 0..7 (0 for passes not run)} of the last cdr_medians_global (HIP events around its launches; src/main.py:31-38,
+ * src/scoring.py:50-54 are what it computes).                              */
+int cdr_medians_global_timing(cdr_ctx* ctx, double* out);
+
 /* ---- access-log group-by: src/compute_features.py:31-54 ---------------- */
 /* Events: file index (row of the manifest, -1 = path not in the manifest),
  * op (1 = WRITE, 2 = READ, other = neither), client id (-1 = null),
