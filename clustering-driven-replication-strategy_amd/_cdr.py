@@ -34,6 +34,9 @@ CDR_ERR_UNSUPPORTED = 5
 MODE_F32X = 1
 MODE_F64 = 2
 SEED_BLOCK = 8192
+PLAN_SLOT = 64            # bytes per tail slot of cdr_plan_format
+PLAN_MAX_TAIL = PLAN_SLOT - 1
+PLAN_MAX_FIELD = 65535    # a longer path field is deferred
 
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -154,6 +157,11 @@ SIGNATURES = {
     "cdr_csv_read": ([_P, _P, _I64, _I64, _I32, _P, _I32, _P, _P, _P, _I64], None),
     "cdr_csv_read_finish": ([_P, _P, _P, _I64, _P], None),
     "cdr_csv_read_timing": ([_P, _P], None),
+    "cdr_plan_format": ([_P, _P, _I64, _I64, _I32, _I32, _P, _I64, _I32, _P, _P, _I64, _I64, _P,
+                         _I64, _P, _P, _I64], None),
+    "cdr_plan_bound": ([_I64, _I64, _PI64], None),
+    "cdr_plan_timing": ([_P, _P], None),
+    "cdr_plan_size_sums": ([_P, _P, _I64, _I32, _P, _P], None),
     "cdr_host_seq_sum": ([_P, _I64, _F64], ctypes.c_double),
 }
 
@@ -1137,6 +1145,92 @@ class Context:
         out = np.zeros(4, dtype=np.float64)
         _check(self._lib.cdr_csv_read_timing(self._h, _ptr(out)))
         return out
+
+    # -- the replication plan on the device (csrc/plan.hip) ------------------
+    def plan_format(self, data, body_off: int, n_cols: int, path_col: int, labels, k: int, tails,
+                    row_begin: int = 0, row_count: int | None = None, out=None,
+                    deferred_cap: int = 1 << 20):
+        """The plan rows ``path,cluster,category,replication\\n`` of the records
+        [row_begin, row_begin + row_count) of the features CSV `data` (the
+        whole file, bytes-like), without a header (include/cdr.h
+        cdr_plan_format).  `labels`: int64 (n) or None for the resident labels;
+        `tails`: k byte strings ``,<category>,<factor>\\n`` of at most
+        ``PLAN_MAX_TAIL`` bytes.  `out`: a uint8 array to format into (too
+        small: ValueError).  Without it the text goes into a buffer the context
+        keeps and grows to what the rows need (a second call when the first
+        guess of 96 bytes per row is short), so the returned text is valid until
+        the next plan_format.  Returns {"rows" (of the file), "text" (a view of
+        the buffer), "deferred_rows", "deferred" (m, 4) int64 {row, offset in
+        text, byte begin, byte end}, "guard"}."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        k = int(k)
+        if len(tails) != k:
+            raise ValueError("one tail per cluster")
+        tl = np.array([len(t) for t in tails], dtype=np.int32)
+        slots = np.zeros((max(k, 1), PLAN_SLOT), dtype=np.uint8)
+        for j, t in enumerate(tails):
+            slots[j, :min(len(t), PLAN_SLOT)] = np.frombuffer(t[:PLAN_SLOT], dtype=np.uint8)
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        count = (1 << 62) if row_count is None else int(row_count)
+        rows_most = min(count, buf.size)  # (a record has at least one byte)
+        own = out is None
+        if own:
+            out = getattr(self, "_plan_buf", None)
+            want = min(self.plan_bound(rows_most, buf.size - int(body_off)), 96 * rows_most + 4096)
+            if out is None or out.size < want:
+                out = self._plan_buf = np.empty(max(want, 1), dtype=np.uint8)
+        cap = max(int(deferred_cap), 0)
+        deferred = np.empty((max(min(cap, rows_most), 1), 4), dtype=np.int64)
+        status = np.zeros(4, dtype=np.int64)
+
+        def call(begin):
+            return self._lib.cdr_plan_format(
+                self._h, _ptr(buf) if buf.size else None, buf.size, int(body_off), int(n_cols),
+                int(path_col), None if lab is None else _ptr(lab), 0 if lab is None else lab.size,
+                k, _ptr(slots), _ptr(tl), begin, count, _ptr(out), out.size, _ptr(status),
+                _ptr(deferred), min(cap, len(deferred)))
+
+        rc = call(int(row_begin))
+        if rc == CDR_ERR_ARG and own and int(status[1]) > out.size:
+            # the rows need more: the index stayed on the device (cdr.h)
+            out = self._plan_buf = np.empty(int(status[1]), dtype=np.uint8)
+            rc = call(int(row_begin))
+        del buf  # (an exception's traceback must not keep the caller's mmap exported)
+        _check(rc)
+        m = min(int(status[2]), len(deferred), cap)
+        return {"rows": int(status[0]), "text": out[:int(status[1])],
+                "deferred_rows": int(status[2]), "deferred": deferred[:m].copy(),
+                "guard": int(status[3])}
+
+    def plan_bound(self, n_rows: int, field_bytes: int) -> int:
+        """cdr_plan_bound: bytes that always hold the text of n_rows rows whose
+        path fields have field_bytes bytes in all."""
+        v = _I64()
+        _check(self._lib.cdr_plan_bound(int(n_rows), int(field_bytes), ctypes.byref(v)))
+        return int(v.value)
+
+    def plan_timing(self) -> np.ndarray:
+        """{upload, record index, lengths + scan, emit, copies} ms of the last plan."""
+        out = np.zeros(5, dtype=np.float64)
+        _check(self._lib.cdr_plan_timing(self._h, _ptr(out)))
+        return out
+
+    def plan_size_sums(self, sizes, k: int, labels=None) -> list:
+        """Per cluster the exact sum (a Python int) of the int64 `sizes` >= 0 of
+        its rows (cdr_plan_size_sums); sizes None: the number of its rows;
+        labels None: the resident labels."""
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        n = lab.size if lab is not None else self.info()["n"]
+        if sizes is not None:
+            sizes = np.ascontiguousarray(sizes, dtype=np.int64).ravel()
+            if lab is not None and lab.size != sizes.size:
+                raise ValueError("one size per label")
+            n = sizes.size
+        out = np.zeros((max(int(k), 1), 2), dtype=np.uint64)
+        _check(self._lib.cdr_plan_size_sums(self._h, None if lab is None else _ptr(lab), n, int(k),
+                                            _ptr(sizes) if sizes is not None and n else None,
+                                            _ptr(out)))
+        return [int(out[j, 0]) + (int(out[j, 1]) << 32) for j in range(int(k))]
 
 
 def _pack_strings(strs):

@@ -351,6 +351,22 @@ struct Ctx {
       cin_def;
   bool cin_pending = false;
   double cin_ms[4] = {0.0, 0.0, 0.0, 0.0};
+  // plan.hip (the record index is csvin.hip's, in the cin_ buffers): explicit
+  // labels as int32, the per-cluster tails (64-byte slots, length in byte 63),
+  // per row of a chunk the path field's offset and length (-1 deferred) and the
+  // output offset, the workgroup sums, the deferred list, the text and its
+  // pinned copy; the sizes and the (k, 2) sums of cdr_plan_size_sums.
+  // plan_rows: records of the indexed file, -1 when no index is resident (a
+  // csv_read or a failed call clears it); plan_nb its body bytes, plan_k and
+  // plan_resident the labels' k and whether they are the context's own;
+  // {upload, record index, lengths + scan, emit, copies} ms of the last plan
+  DevBuf plan_lab, plan_tails, plan_fstart, plan_flen, plan_rowoff, plan_part, plan_def, plan_out,
+      plan_sz, plan_sum;
+  HostBuf plan_host;
+  int64_t plan_rows = -1, plan_nb = 0;
+  int32_t plan_k = 0;
+  bool plan_resident = false;
+  double plan_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   // clusters of the grouped rows (cdr_medians_group); 0 = none: whatever
   // replaces the points, rewrites the labels or reuses med_vals / med_off /
   // med_out (medians_segmented) clears it, and the pass entries refuse to run.
@@ -415,6 +431,9 @@ void points_finish_analysis(Ctx& c);
 // points_analyze_and_store ends.
 void points_begin_resident(Ctx& c, int64_t n, int32_t d);
 void points_finish_resident(Ctx& c);
+// csvin.hip: the record index of the body in c.cin_bytes (see there)
+void csv_index_count(Ctx& c, int64_t nb, long long* r8);
+void csv_index_write(Ctx& c, int64_t nb, int64_t nrec, bool tail);
 
 void lloyd_step_f32x(Ctx& c, const double* C, int32_t k, int64_t* out,
                      bool out_on_device);

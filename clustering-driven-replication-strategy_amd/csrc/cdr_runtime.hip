@@ -476,11 +476,14 @@ int cdr_destroy(cdr_ctx* h) {
                     &c.ll_state, &c.q_buf, &c.csv_table, &c.csv_slots, &c.csv_pbytes, &c.csv_poff,
                     &c.csv_qlen, &c.csv_rowoff, &c.csv_part, &c.csv_def, &c.csv_out,
                     &c.cin_bytes, &c.cin_tile, &c.cin_part, &c.cin_mask, &c.cin_ends, &c.cin_sc,
-                    &c.cin_blk, &c.cin_cnt, &c.cin_map, &c.cin_def};
+                    &c.cin_blk, &c.cin_cnt, &c.cin_map, &c.cin_def,
+                    &c.plan_lab, &c.plan_tails, &c.plan_fstart, &c.plan_flen, &c.plan_rowoff,
+                    &c.plan_part, &c.plan_def, &c.plan_out, &c.plan_sz, &c.plan_sum};
   for (DevBuf* b : bufs) b->release();
   c.h_small.release();
   c.h_up.release();
   c.csv_host.release();
+  c.plan_host.release();
   if (c.up_event) (void)hipEventDestroy(c.up_event);
   for (hipEvent_t& e : c.prof_pool)
     if (e) (void)hipEventDestroy(e);

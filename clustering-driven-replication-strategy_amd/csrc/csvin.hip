@@ -30,6 +30,7 @@
 #include <climits>
 
 #include "cdr_internal.h"
+#include "csv_guard.h"
 #include "csv_parse.h"
 
 namespace cdr {
@@ -229,28 +230,6 @@ struct ParseArgs {
   long long* sc;           // sc[1]: first guard offset (atomicMin)
 };
 
-// The first byte of the row [s, e) at which the quote rule fails, or -1.  The
-// row starts outside quotes.  An escaped quote ("" inside quotes) stays inside.
-__device__ int64_t guard_walk(const uint8_t* buf, int64_t s, int64_t e) {
-  bool inq = false;
-  int64_t open = -1;
-  for (int64_t k = s; k < e; ++k) {
-    if (buf[k] != '"') continue;
-    if (!inq) {
-      if (k != s && buf[k - 1] != ',') return k;  // pandas keeps it as a literal
-      inq = true;
-      open = k;
-    } else if (k + 1 < e && buf[k + 1] == '"') {
-      ++k;
-    } else {
-      const uint8_t nx = k + 1 < e ? buf[k + 1] : (uint8_t)',';
-      if (nx != ',' && nx != '\r' && nx != '\n') return k;  // pandas reads on, unquoted
-      inq = false;
-    }
-  }
-  return inq ? open : -1;  // the file ends inside quotes
-}
-
 // One record: buf = the bytes from a0 on (LDS stage or global), st = position
 // (relative to a0) just after the previous record, e0 = position of this
 // record's terminator.  Returns bit 0: the row is deferred, bit 1: its cells were
@@ -435,6 +414,40 @@ struct Events {
 
 }  // namespace
 
+// The record index of the body in c.cin_bytes (nb > 0 bytes, zero-padded to a
+// whole tile and one more), for csv_read and plan.hip.  csv_index_count runs
+// q_count, the scan and q_total and reads c.cin_sc back into r8 (r8[0] records,
+// r8[5] the tail record, r8[6] the final parity); csv_index_write then fills
+// c.cin_ends[0, nrec) (the caller has sized it).
+void csv_index_count(Ctx& c, int64_t nb, long long* r8) {
+  const int64_t ntiles = ceil_div(nb, kTile);
+  const uint8_t* db = c.cin_bytes.as<uint8_t>();
+  long long* sc = c.cin_sc.as<long long>();
+  c.cin_tile.ensure(sizeof(QE) * (2 * ntiles + 1));
+  QE* tile = c.cin_tile.as<QE>();
+  QE* pre = tile + ntiles;
+  c.cin_mask.ensure(4 * 256 * ntiles);
+  hipLaunchKernelGGL(q_count, dim3(ntiles), dim3(256), 0, c.stream, db, tile,
+                     c.cin_mask.as<uint32_t>());
+  qe_scan(c, tile, ntiles, pre);
+  hipLaunchKernelGGL(q_total, dim3(1), dim3(1), 0, c.stream, pre, ntiles, db, nb, sc);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(r8, sc, 8 * sizeof(long long), hipMemcpyDeviceToHost, c.stream));
+  HIP_CHECK(hipStreamSynchronize(c.stream));
+}
+
+void csv_index_write(Ctx& c, int64_t nb, int64_t nrec, bool tail) {
+  const int64_t ntiles = ceil_div(nb, kTile);
+  hipLaunchKernelGGL(q_write, dim3(ntiles), dim3(256), 0, c.stream, c.cin_mask.as<uint32_t>(),
+                     c.cin_tile.as<QE>() + ntiles, c.cin_ends.as<long long>());
+  HIP_CHECK(hipGetLastError());
+  if (tail) {  // the tail record's end goes last
+    *c.h_small.as<long long>() = nb;
+    HIP_CHECK(hipMemcpyAsync(c.cin_ends.as<long long>() + nrec - 1, c.h_small.p, 8,
+                             hipMemcpyHostToDevice, c.stream));
+  }
+}
+
 void csv_read(Ctx& c, const char* bytes, int64_t nbytes, int64_t body_off, int32_t n_cols,
               const int32_t* sel, int32_t d, int64_t* status, int64_t* col_kinds,
               int64_t* deferred, int64_t deferred_cap) {
@@ -450,6 +463,7 @@ void csv_read(Ctx& c, const char* bytes, int64_t nbytes, int64_t body_off, int32
     colmap[sel[j]] = (int16_t)j;
   }
   c.cin_pending = false;
+  c.plan_rows = -1;  // the index buffers are rewritten
   c.h_small.ensure(64);
   for (double& v : c.cin_ms) v = 0.0;
   const int64_t nb = nbytes - body_off;
@@ -472,18 +486,8 @@ void csv_read(Ctx& c, const char* bytes, int64_t nbytes, int64_t body_off, int32
   long long nrec = 0;
   bool tail = false;
   if (ntiles > 0) {
-    c.cin_tile.ensure(sizeof(QE) * (2 * ntiles + 1));
-    QE* tile = c.cin_tile.as<QE>();
-    QE* pre = tile + ntiles;
-    c.cin_mask.ensure(4 * 256 * ntiles);
-    hipLaunchKernelGGL(q_count, dim3(ntiles), dim3(256), 0, c.stream, db, tile,
-                       c.cin_mask.as<uint32_t>());
-    qe_scan(c, tile, ntiles, pre);
-    hipLaunchKernelGGL(q_total, dim3(1), dim3(1), 0, c.stream, pre, ntiles, db, nb, sc);
-    HIP_CHECK(hipGetLastError());
     long long r8[8];
-    HIP_CHECK(hipMemcpyAsync(r8, sc, sizeof(r8), hipMemcpyDeviceToHost, c.stream));
-    HIP_CHECK(hipStreamSynchronize(c.stream));
+    csv_index_count(c, nb, r8);
     nrec = r8[0];
     tail = r8[5] != 0;
     if (nrec < 0 || nrec > nb) CDR_FAIL(CDR_ERR_STATE, "csv read: inconsistent record count");
@@ -502,14 +506,7 @@ void csv_read(Ctx& c, const char* bytes, int64_t nbytes, int64_t body_off, int32
     c.cin_map.ensure(2 * (size_t)n_cols);
     HIP_CHECK(hipMemcpyAsync(c.cin_map.p, colmap.data(), 2 * (size_t)n_cols, hipMemcpyHostToDevice,
                              c.stream));
-    hipLaunchKernelGGL(q_write, dim3(ntiles), dim3(256), 0, c.stream, c.cin_mask.as<uint32_t>(),
-                       c.cin_tile.as<QE>() + ntiles, c.cin_ends.as<long long>());
-    HIP_CHECK(hipGetLastError());
-    if (tail) {  // the tail record's end goes last
-      *c.h_small.as<long long>() = nb;
-      HIP_CHECK(hipMemcpyAsync(c.cin_ends.as<long long>() + nrec - 1, c.h_small.p, 8,
-                               hipMemcpyHostToDevice, c.stream));
-    }
+    csv_index_write(c, nb, nrec, tail);
     HIP_CHECK(hipEventRecord(ev.e[2], c.stream));
     ParseArgs a;
     a.b = db;

@@ -1,0 +1,379 @@
+"""The per-file replication plan: path, cluster, category, replication factor.
+
+``src/main.py:92`` forms ``feature_file['cluster'] = labels`` and drops it; the
+reference writes one row per centroid.  The plan is the row per file, what one
+hands to ``hdfs dfs -setrep``, and ``summarize`` says what it costs in bytes.
+
+The plan is defined by ``write_plan_csv_host`` and by nothing else::
+
+    frame = pd.read_csv(src, usecols=[path_column], dtype=str, keep_default_na=False,
+                        na_filter=False)
+    w = csv.writer(out, lineterminator="\\n")
+    w.writerow(["path", "cluster", "category", "replication"])
+    for p, l in zip(frame[path_column], labels):
+        w.writerow([p, int(l), category_of_cluster[l], replication_factors[category_of_cluster[l]]])
+
+``write_plan_csv`` gives the same bytes with the rows formatted in libcdr.so
+(csrc/plan.hip): the paths are copied as bytes from the features CSV that
+``kmeans_csv`` read, and the labels of the last assignment never leave the
+device.  What the device does not decide itself goes to the definition, never
+to a guess: a deferred row (a quote, a NUL, a lone CR, a field count other than
+the header's, a path longer than 65535 bytes) is formatted by the host and
+spliced in; the whole file goes to the host writer in the cases where
+``read_features`` takes the whole file to pandas.  The file must be UTF-8, as
+pandas requires.
+
+CLI (the join of ``size_bytes`` on ``path`` for ``--manifest`` is host work, pandas)::
+
+    python replication_plan.py --input_path F --k K --tables T.json --out plan.csv
+                               [--manifest M.csv] [--current_factor R]
+"""
+from __future__ import annotations
+
+import argparse
+import csv
+import glob
+import io
+import json
+import mmap
+import os
+import time
+
+import numpy as np
+
+from _cdr import PLAN_MAX_TAIL, Context, default_context
+
+__all__ = ["HEADER", "write_plan_csv", "write_plan_csv_host", "summarize", "main"]
+
+HEADER = ["path", "cluster", "category", "replication"]
+MAX_K = 1024                  # cdr_plan_format's k
+DEFERRED_CAP = 1 << 20        # deferred rows taken back from the device per call
+# Rows per cdr_plan_format call.  Beyond the file and its record index (8 B per
+# row), a call keeps 8 + 4 + 8 B per row of field offsets, lengths and output
+# offsets and the chunk's text (about 50 B per row for paths of 30 bytes) on
+# the device, pinned on the host, and once more in the buffer the context keeps
+# for the text (96 B per row, grown to what a chunk needs): 2^18 rows bound each
+# at about 25 MiB whatever the file's size, and still give every CU several
+# workgroups.
+PLAN_CHUNK_ROWS = 1 << 18
+
+
+class _Bytes:
+    """csv.writer target that collects UTF-8 bytes (newline="" semantics)."""
+
+    def __init__(self):
+        self.parts = []
+
+    def write(self, text):
+        self.parts.append(text.encode("utf-8"))
+
+
+def _tables(categories, replication_factors, prefix="C", k=None):
+    """(category of cluster j, factor of cluster j) for j < k (default: the
+    number of entries of `categories`)."""
+    k = len(categories) if k is None else int(k)
+    cats, facs = [], []
+    for j in range(k):
+        name = f"{prefix}{j}"
+        if name not in categories:
+            raise ValueError(f"cluster {name} has no category")
+        cat = categories[name]
+        if cat not in replication_factors:
+            raise ValueError(f"category {cat!r} has no replication factor")
+        fac = replication_factors[cat]
+        if isinstance(fac, bool) or not isinstance(fac, (int, np.integer)) or fac < 0:
+            raise ValueError(f"the replication factor of {cat!r} is not an int >= 0: {fac!r}")
+        cats.append(cat)
+        facs.append(int(fac))
+    return cats, facs
+
+
+def _label(l, k):
+    l = int(l)
+    if not 0 <= l < k:
+        raise ValueError(f"cluster {l} has no category")
+    return l
+
+
+def write_plan_csv_host(src, out, categories, replication_factors, *, labels=None,
+                        path_column="path", prefix="C", chunk_rows=None, info=None) -> int:
+    """The definition of the plan (module docstring); returns the row count.
+    ``labels``: one cluster per row of ``src`` (there are no resident labels on
+    the host); ``chunk_rows`` is accepted for the common signature and unused."""
+    import pandas as pd
+
+    cats, facs = _tables(categories, replication_factors, prefix)
+    if labels is None:
+        raise ValueError("the host writer needs the labels")
+    frame = pd.read_csv(src, usecols=[path_column], dtype=str, keep_default_na=False,
+                        na_filter=False)
+    labels = np.asarray(labels).ravel()
+    if len(labels) != len(frame):
+        raise ValueError(f"{len(labels)} labels, the file has {len(frame)} rows")
+    with open(out, "w", newline="", encoding="utf-8") as fh:
+        w = csv.writer(fh, lineterminator="\n")
+        w.writerow(HEADER)
+        for p, l in zip(frame[path_column], labels):
+            l = _label(l, len(cats))
+            w.writerow([p, l, cats[l], facs[l]])
+    if info is not None:
+        info.clear()
+        info.update(rows=len(frame), deferred_rows=0, whole_file_fallback=True)
+    return len(frame)
+
+
+def _tail(cat, fac) -> bytes:
+    """``,<category>,<factor>\\n`` as csv.writer writes it after two fields."""
+    sink = _Bytes()
+    csv.writer(sink, lineterminator="\n").writerow(["", cat, fac])
+    return b"".join(sink.parts)
+
+
+def _splice(text, deferred, data, body, names, path_column, labels, cats, facs):
+    """The chunk's text with the definition's rows at the deferred rows'
+    offsets, or None when pandas' view of those rows does not line up with the
+    device's (the whole file goes to the host writer then)."""
+    import pandas as pd
+
+    parts = [bytes(data[:body])]
+    if not parts[0].endswith(b"\n"):
+        parts.append(b"\n")
+    # pandas infers an index from a first data row with more fields than the
+    # header; a plain first row (dropped below) keeps the header's meaning
+    parts.append(b",".join([b"0"] * len(names)) + b"\n")
+    for _, _, b0, b1 in deferred:
+        parts.append(bytes(data[int(b0):int(b1)]))
+        parts.append(b"\n")
+    try:
+        frame = pd.read_csv(io.BytesIO(b"".join(parts)), usecols=[path_column], dtype=str,
+                            keep_default_na=False, na_filter=False)
+    except Exception:
+        return None
+    if len(frame) != len(deferred) + 1:  # (a lone CR ends a record for pandas)
+        return None
+    sink = _Bytes()
+    w = csv.writer(sink, lineterminator="\n")
+    text = memoryview(text)
+    pos = 0
+    for (row, off, _, _), p in zip(deferred, frame[path_column][1:]):
+        sink.parts.append(bytes(text[pos:off]))
+        pos = int(off)
+        l = int(labels[int(row)])
+        w.writerow([p, l, cats[l], facs[l]])
+    sink.parts.append(bytes(text[pos:]))
+    return b"".join(sink.parts)
+
+
+def write_plan_csv(src, out, categories, replication_factors, *, labels=None, path_column="path",
+                   prefix="C", context: Context | None = None, chunk_rows=None,
+                   info: dict | None = None) -> int:
+    """``write_plan_csv_host`` with the rows formatted on the device, byte for
+    byte the same file; returns the row count.  ``categories`` is what
+    ``ClusterClassifier.classify_labels`` returns; ``labels=None`` takes the
+    labels of the last assignment resident in ``context`` (after ``kmeans_csv``
+    of the same file, row i is point i).  One library call and one binary write
+    per ``chunk_rows`` rows (default ``PLAN_CHUNK_ROWS``); the text does not
+    depend on the chunking.
+
+    ``info`` (a dict, filled in place) receives ``rows``, ``deferred_rows``,
+    ``whole_file_fallback`` and the times ``upload_ms``, ``index_ms``,
+    ``length_ms``, ``emit_ms``, ``copy_ms`` (cdr_plan_timing: device events) and,
+    on the host clock, ``call_ms`` (inside the library calls) and ``write_ms``
+    (writing the text to the file)."""
+    from features_csv import _first_row_fields, _header
+
+    ctx = context if context is not None else default_context()
+    info = info if info is not None else {}
+    info.clear()
+    cats, facs = _tables(categories, replication_factors, prefix)
+    k = len(cats)
+    chunk = PLAN_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)
+    if chunk < 1:
+        raise ValueError("chunk_rows must be at least 1")
+    if labels is not None:
+        labels = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+    tails = [_tail(c, f) for c, f in zip(cats, facs)]
+
+    def whole_file():
+        lab = labels if labels is not None else ctx.labels()
+        return write_plan_csv_host(src, out, categories, replication_factors, labels=lab,
+                                   path_column=path_column, prefix=prefix, info=info)
+
+    size = os.path.getsize(src)
+    if size == 0 or not 1 <= k <= MAX_K or max(len(t) for t in tails) > PLAN_MAX_TAIL:
+        return whole_file()  # (an empty file: pandas' EmptyDataError)
+    ok = True
+    with open(src, "rb") as fh, mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) as data:
+        head = _header(data)
+        if head is None:
+            return whole_file()
+        names, body = head
+        plain = (len(set(names)) == len(names) and all(names) and len(names) <= 32767
+                 and path_column in names and body < size
+                 and _first_row_fields(data, body) in (-1, len(names)))
+        if not plain:
+            # names pandas would mangle, a first row that makes pandas infer an
+            # index, no such column (pandas' own error), no data rows
+            return whole_file()
+        col = names.index(path_column)
+        n_deferred, call_s, write_s = 0, 0.0, 0.0
+        # the text goes to a name of its own until it is whole: an error (a label
+        # out of range, ...) leaves no plan file, a fallback no half-written one
+        part = f"{out}.part"
+        try:
+            with open(part, "wb") as fo:
+                fo.write((",".join(HEADER) + "\n").encode("utf-8"))
+                lo = 0
+                while ok:
+                    t0 = time.perf_counter()
+                    try:
+                        res = ctx.plan_format(data, body, len(names), col, labels, k, tails, lo,
+                                              chunk, deferred_cap=DEFERRED_CAP)
+                    except ValueError as e:
+                        if "the file has" not in str(e):
+                            raise
+                        # the label count is not the device's row count: pandas' rows
+                        # decide (a lone CR ends a record for pandas alone)
+                        ok = False
+                        break
+                    t1 = time.perf_counter()
+                    call_s += t1 - t0
+                    n, text = res["rows"], res["text"]
+                    if res["guard"] >= 0 or res["deferred_rows"] > len(res["deferred"]):
+                        ok = False
+                        break
+                    if res["deferred_rows"]:
+                        lab = labels if labels is not None else ctx.labels()
+                        text = _splice(text, res["deferred"], data, body, names, path_column, lab,
+                                       cats, facs)
+                        if text is None:
+                            ok = False
+                            break
+                        n_deferred += res["deferred_rows"]
+                    t1 = time.perf_counter()
+                    fo.write(memoryview(text))
+                    write_s += time.perf_counter() - t1
+                    lo += chunk
+                    if lo >= n:
+                        break
+            if ok:
+                os.replace(part, out)
+        finally:
+            if os.path.exists(part):
+                os.remove(part)
+    if not ok:
+        return whole_file()
+    t = ctx.plan_timing()
+    info.update(rows=n, deferred_rows=n_deferred, whole_file_fallback=False,
+                upload_ms=float(t[0]), index_ms=float(t[1]), length_ms=float(t[2]),
+                emit_ms=float(t[3]), copy_ms=float(t[4]), call_ms=1e3 * call_s,
+                write_ms=1e3 * write_s)
+    return n
+
+
+def summarize(categories, replication_factors, k, *, sizes=None, current_factor=None, labels=None,
+              context: Context | None = None, prefix="C") -> dict:
+    """What the plan holds and costs: ``{"categories": {category: {...}},
+    "total": {...}}`` with, per category, ``factor``, ``clusters`` (their
+    numbers), ``files``; with ``sizes`` (int64 >= 0, one per file) also ``bytes``
+    and ``replica_bytes = factor * bytes``; with ``current_factor`` (HDFS's one
+    ``dfs.replication`` of all files) also ``bytes_to_copy = max(factor -
+    current, 0) * bytes`` and ``bytes_to_free = max(current - factor, 0) *
+    bytes``.  ``total`` sums them over the categories.  ``labels=None``: the
+    labels resident in ``context``.  The per-cluster counts and size sums come
+    from the device (cdr_plan_size_sums); the rest is arithmetic on k Python
+    ints."""
+    ctx = context if context is not None else default_context()
+    k = int(k)
+    cats, facs = _tables(categories, replication_factors, prefix, k)
+    if current_factor is not None and (isinstance(current_factor, bool)
+                                       or not isinstance(current_factor, (int, np.integer))
+                                       or current_factor < 0):
+        raise ValueError(f"current_factor is not an int >= 0: {current_factor!r}")
+    if labels is not None:
+        labels = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        n = labels.size
+    else:
+        n = ctx.info()["n"]
+    if sizes is not None:
+        sizes = np.ascontiguousarray(sizes, dtype=np.int64).ravel()
+        if sizes.size != n:
+            raise ValueError(f"{sizes.size} sizes for {n} files")
+    files = ctx.plan_size_sums(None, k, labels)  # no sizes: the rows are counted
+    nbytes = ctx.plan_size_sums(sizes, k, labels) if sizes is not None else None
+    keys = ["files"] + (["bytes", "replica_bytes"] if sizes is not None else []) + (
+        ["bytes_to_copy", "bytes_to_free"] if sizes is not None and current_factor is not None
+        else [])
+    out = {}
+    for j in range(k):
+        row = out.setdefault(cats[j], dict({"factor": facs[j], "clusters": []},
+                                           **{key: 0 for key in keys}))
+        row["clusters"].append(j)
+        row["files"] += files[j]
+        if nbytes is not None:
+            row["bytes"] += nbytes[j]
+            row["replica_bytes"] += facs[j] * nbytes[j]
+            if current_factor is not None:
+                row["bytes_to_copy"] += max(facs[j] - int(current_factor), 0) * nbytes[j]
+                row["bytes_to_free"] += max(int(current_factor) - facs[j], 0) * nbytes[j]
+    total = {key: sum(row[key] for row in out.values()) for key in keys}
+    return {"categories": out, "total": total}
+
+
+def _resolve(input_path):
+    """src/main.py:154-168: a directory holds part-00000*.csv; the first match."""
+    pattern = os.path.join(input_path, "part-00000*.csv") if os.path.isdir(input_path) \
+        else input_path
+    found = glob.glob(pattern)
+    if not found:
+        raise SystemExit(f"Error: No features CSV file found matching pattern: {pattern}")
+    return found[0]
+
+
+def main(argv=None, context: Context | None = None):
+    from features_csv import CLUSTERING_FEATURES, kmeans_csv
+    from scoring import ClusterClassifier
+
+    ap = argparse.ArgumentParser(description="Cluster the features CSV and write the per-file "
+                                             "replication plan.")
+    ap.add_argument("--input_path", required=True)
+    ap.add_argument("--k", type=int, default=4)
+    ap.add_argument("--tables", required=True,
+                    help="JSON with WEIGHTS, DIRECTIONS, REPLICATION_FACTORS and optionally "
+                         "GLOBAL_MEDIANS")
+    ap.add_argument("--out", default="plan.csv")
+    ap.add_argument("--manifest", default=None, help="CSV with path and size_bytes columns")
+    ap.add_argument("--current_factor", type=int, default=None)
+    args = ap.parse_args(argv)
+    src = _resolve(args.input_path)
+    with open(args.tables) as fh:
+        t = json.load(fh)
+    ctx = context if context is not None else default_context()
+    kmeans_csv(src, args.k, random_state=42, context=ctx)
+    if "GLOBAL_MEDIANS" in t:
+        clf = ClusterClassifier(t["GLOBAL_MEDIANS"], t["WEIGHTS"], t["DIRECTIONS"],
+                                t["REPLICATION_FACTORS"], context=ctx)
+    else:
+        clf = ClusterClassifier.from_points(t["WEIGHTS"], t["DIRECTIONS"],
+                                            t["REPLICATION_FACTORS"], CLUSTERING_FEATURES,
+                                            context=ctx)
+    categories = clf.classify_labels(args.k, CLUSTERING_FEATURES, context=ctx)
+    rows = write_plan_csv(src, args.out, categories, t["REPLICATION_FACTORS"], context=ctx)
+    print(f"Wrote the plan of {rows} files to {args.out}")
+    if args.manifest:
+        import pandas as pd
+
+        paths = pd.read_csv(src, usecols=["path"], dtype=str, keep_default_na=False,
+                            na_filter=False)["path"]
+        man = pd.read_csv(args.manifest, usecols=["path", "size_bytes"],
+                          dtype={"path": str}, keep_default_na=False, na_filter=False)
+        sizes = paths.map(man.drop_duplicates("path").set_index("path")["size_bytes"])
+        if sizes.isna().any():
+            raise SystemExit(f"Error: {int(sizes.isna().sum())} paths are not in the manifest")
+        print(json.dumps(summarize(categories, t["REPLICATION_FACTORS"], args.k,
+                                   sizes=sizes.to_numpy(dtype=np.int64),
+                                   current_factor=args.current_factor, context=ctx)))
+
+
+if __name__ == "__main__":
+    main()

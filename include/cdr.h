@@ -637,6 +637,68 @@ int cdr_csv_read_finish(cdr_ctx* ctx, const int64_t* rows, const double* values,
                         double* X_out);
 int cdr_csv_read_timing(cdr_ctx* ctx, double* out);
 
+/* ---- the per-file replication plan (extension: src/main.py:92 forms the ---- */
+/* ---- cluster column and drops it) ---------------------------------------- */
+/* One text row "path,cluster,category,replication\n" per record of the features
+ * CSV, without the header row, in record order (row i belongs to label i, the
+ * alignment cdr_csv_read gives the points).
+ *
+ * cdr_plan_format: bytes[0, nbytes) is the whole file, body_off the offset of
+ *   the first byte after the header record, n_cols the header's field count
+ *   (1..32767, else CDR_ERR_UNSUPPORTED), path_col the path's column.  labels:
+ *   n_labels host values in [0, k), or NULL for the labels of the last
+ *   assignment resident in the context (n_labels is then ignored); 1 <= k <=
+ *   1024 (else CDR_ERR_UNSUPPORTED).  tails: k slots of 64 bytes, slot j holding
+ *   the tail_len[j] <= 63 bytes ",<category>,<factor>\n" of cluster j as the
+ *   caller's csv.writer wrote them (the device never quotes).
+ *   The records are found exactly as cdr_csv_read finds them.  A row's text is
+ *   its path_col field as it stands in the file, ',', the decimal label and
+ *   the tail.  The call formats the records [row_begin, row_begin + row_count)
+ *   (clipped to the file's): a call with row_begin == 0 uploads the file and
+ *   builds the record index, which stays on the device for the following calls
+ *   with row_begin > 0 and the same file, k and kind of labels (CDR_ERR_STATE
+ *   without it; cdr_csv_read and a failed call drop it).  Resident labels are
+ *   checked again on every call.  Device scratch beyond
+ *   the file and its index is bounded by row_count; the text does not depend on
+ *   the split.
+ *   A row is deferred when it holds a '"', a NUL or a '\r' that is not before
+ *   its '\n', when its field count differs from n_cols, or when its path field
+ *   is longer than 65535 bytes.  It adds no bytes to out and is listed in
+ *   deferred as {row, byte offset in out where its text belongs, byte begin,
+ *   byte end} (the row of the file; file offsets, the terminator excluded), in
+ *   row order; deferred receives min(status[2], deferred_cap) entries.
+ *   status[0] = rows of the file, status[1] = bytes in out, status[2] = deferred
+ *   rows of this call, status[3] = cdr_csv_read's status[2] (the guard) over the
+ *   rows formatted since row_begin == 0, -1 if none: with it >= 0 the rows are
+ *   not pandas' rows and the caller takes the whole file to the host.
+ *   CDR_ERR_ARG, with nothing written to out or deferred, for a label outside
+ *   [0, k), a label count (the context's row count for resident labels) other
+ *   than the file's row count, k below the resident labels' k, a tail longer
+ *   than 63 bytes, or cap below what the rows need (the bound always suffices;
+ *   status[1] then holds what they need and the index stays for a second call);
+ *   CDR_ERR_STATE without labels on the device when labels == NULL.  The
+ *   context's points, labels and grouped medians are not touched.
+ * cdr_plan_bound (host only): field_bytes + n_rows * (1 + 10 + 63), with
+ *   field_bytes an upper bound of the rows' path bytes (the body's size is one).
+ * cdr_plan_timing: out[5] = {upload, record index, lengths + scan kernels,
+ *   emit kernel, copies back} ms, summed over the calls since row_begin == 0.
+ * cdr_plan_size_sums: what the plan costs.  For cluster j of labels (n host
+ *   values in [0, k), or NULL: the resident labels, n = the context's rows) and
+ *   sizes (n host values >= 0, n < 2^31): out[2 j] = the sum of the sizes' low 32
+ *   bits, out[2 j + 1] = the sum of their high 31 bits (neither can overflow;
+ *   total = out[2 j] + out[2 j + 1] * 2^32).  sizes == NULL counts the rows:
+ *   every size is 1 and nothing is uploaded.  CDR_ERR_ARG for a negative size,
+ *   a label out of range, or n other than the context's rows with NULL labels. */
+int cdr_plan_format(cdr_ctx* ctx, const char* bytes, int64_t nbytes, int64_t body_off,
+                    int32_t n_cols, int32_t path_col, const int64_t* labels, int64_t n_labels,
+                    int32_t k, const char* tails, const int32_t* tail_len, int64_t row_begin,
+                    int64_t row_count, char* out, int64_t cap, int64_t* status, int64_t* deferred,
+                    int64_t deferred_cap);
+int cdr_plan_bound(int64_t n_rows, int64_t field_bytes, int64_t* bytes);
+int cdr_plan_timing(cdr_ctx* ctx, double* out);
+int cdr_plan_size_sums(cdr_ctx* ctx, const int64_t* labels, int64_t n, int32_t k,
+                       const int64_t* sizes, uint64_t* out /* [k][2] */);
+
 /* ---- cluster quality (extension: no reference counterpart) ------------- */
 /* Validity indices of a clustering of the resident points, for choosing the
  * k the reference fixes (src/main.py --k).  The distance is the reference's
