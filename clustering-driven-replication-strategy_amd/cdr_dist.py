@@ -439,7 +439,7 @@ def shard_scan(ctx, comm: Comm, parts, total: float):
 
 def device_seed_layout_ok(offsets, n_total: int, world: int) -> bool:
     """Whether the ranks' row layout fits the device-resident protocol
-    (csrc/seed.hip seed_shard_begin): shards in rank order from row 0, every
+    (csrc/seed_run.hip seed_shard_begin): shards in rank order from row 0, every
     start on an 8192-row block, and no shard over ceil(blocks / world) blocks
     (the [nranks][nbmax] block-sum slots).  Decided from the all-gathered
     offsets, so every rank takes the same branch: a layout the device

@@ -293,7 +293,7 @@ struct Ctx {
   // ---- seeding ----
   DevBuf dmin;        // double[n_pad]
   DevBuf dmin32, bs32;  // float32 reference runs: fp32 dist_sq [n_pad], chunk sums
-  // exact pruning of the seeding update (seed.hip seed_prunable): the index
+  // exact pruning of the seeding update (seed_update.hip seed_prunable): the index
   // of each point's nearest centre so far, the centres, their distances to
   // the newest one
   DevBuf seed_near;   // int32[n_pad]
@@ -303,21 +303,21 @@ struct Ctx {
   DevBuf blocksums;   // double[nblocks]
   DevBuf xfer;        // per-block transfer records
   DevBuf cend;        // double[nblocks] running value after each block
-  DevBuf seg_tails, seg_ents, seg_scan, seg_items, seg_meta;  // cumsum program (seed.hip)
+  DevBuf seg_tails, seg_ents, seg_scan, seg_items, seg_meta;  // cumsum program (seed_scan.hip)
   double seed_prog_total = 0.0;
   bool seed_prog_ready = false;
   long long seed_programs = 0;   // scans run through a cumsum program
   long long seed_fallbacks = 0;  // programs whose guess failed (block walk instead)
-  DevBuf seed_x16, seed_e16, seed_mu;  // fp16-certified seeding copy (seed.hip)
+  DevBuf seed_x16, seed_e16, seed_mu;  // fp16-certified seeding copy (seed_update.hip)
   bool seed16_valid = false;
   DevBuf seed_run_buf;  // seed_run: uniforms, picks, S, flags
-  // device-resident seeding over sharded rows (seed.hip cdr_seed_shard_*):
+  // device-resident seeding over sharded rows (seed_run.hip cdr_seed_shard_*):
   // [u: k-1][picks: k][S, guess, c_mine, c_after, c_last, flags x4, pad]
   DevBuf ss_buf;
   int64_t ss_row_begin = 0, ss_n_total = 0, ss_nbmax = 0;
   int32_t ss_nranks = 0, ss_rank = 0, ss_k = 0, ss_step = 0;
   bool ss_on = false;
-  DevBuf seed_tail_plan;  // pairwise layout of the partial last block (seed.hip)
+  DevBuf seed_tail_plan;  // pairwise layout of the partial last block (seed_update.hip)
   int64_t seed_tail_m = -1;
   int seed_tail_nleaves = 0, seed_tail_nheights = 0;
   DevBuf seed_scalar; // small device scratch

@@ -11,7 +11,7 @@
 // parity, so a run of additions inside one binade is an integer transfer that
 // depends only on the parity of m when the run starts: (D0, P0) for an even
 // entry and (D1, P1) for an odd one (the same idea as the seeding cumsum,
-// csrc/seed.hip).
+// csrc/seed_common.h).
 //
 //   A  f64_blocksum   per 256-row block: approximate per-(cluster, feature)
 //                     sums (any order) and member counts

@@ -357,7 +357,7 @@ __global__ void aos_copy_kernel(const float4* __restrict__ x, int64_t n_pad, int
 }
 
 // The row-major copy, built once per point set (also the large-k path's
-// gathers, screen_big.hip, and the seeding's, seed.hip).
+// gathers, screen_big.hip, and the seeding's, seed_update.hip).
 void ensure_rowmajor(Ctx& c) {
   if (c.xa_valid) return;
   const int Q = d4_of(c.d) / 4;

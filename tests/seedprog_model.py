@@ -1,5 +1,5 @@
 """Python model of a shard's cumsum program (include/cdr.h cdr_seed_item,
-csrc/seed.hip seg_block_kernel) for the CPU tests: runs of elements whose
+csrc/seed_scan.hip seg_block_kernel) for the CPU tests: runs of elements whose
 guessed running value stays in one binade become RUN transfers, every other
 element a CROSS.  Test infrastructure only (the device builds the real
 programs); it lets the host evaluator and the sharded protocol be checked
@@ -21,7 +21,7 @@ def binade(c: float):
 
 
 def near(c: float) -> bool:
-    """Within 2^-24 of a binade edge (csrc/seed.hip gnear)."""
+    """Within 2^-24 of a binade edge (csrc/seed_scan.hip gnear)."""
     m = int(np.float64(c).view(np.uint64)) & ((1 << 52) - 1)
     return m < (1 << 28) or m > (1 << 52) - (1 << 28)
 

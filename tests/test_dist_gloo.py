@@ -201,7 +201,7 @@ def test_two_ranks_match_single_process(tmp_path, world, empty):
 
 class DeviceSeedShard(OracleShard):
     """The device-resident sharded seeding protocol (include/cdr.h
-    cdr_seed_shard_*, csrc/seed.hip) on the oracle: every phase reads and
+    cdr_seed_shard_*, csrc/seed_run.hip) on the oracle: every phase reads and
     writes the exchanged byte buffers in the layout the kernels use (red:
     row | global index + 1 | fail | nan | pad as float64; block sums
     [nranks][nbmax]; programs [nranks][1024] cdr_seed_item with a count
@@ -239,7 +239,7 @@ class DeviceSeedShard(OracleShard):
     def seed_shard_begin(self, row_begin, n_total, nranks, rank, first, k, u, red):
         self.rb, self.W, self.r, self.k, self.u = row_begin, nranks, rank, k, np.asarray(u)
         self.nbmax = -(-(-(-n_total // 8192)) // nranks)
-        # the kernel's layout checks (csrc/seed.hip seed_shard_begin)
+        # the kernel's layout checks (csrc/seed_run.hip seed_shard_begin)
         if row_begin % 8192 != 0 and self.X.shape[0] > 0:
             raise ValueError("shards must start on an 8192-row block")
         if -(-self.X.shape[0] // 8192) > self.nbmax:

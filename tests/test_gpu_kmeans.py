@@ -279,15 +279,33 @@ def test_seeding_many_blocks_vs_oracle(ctx, n, outlier):
     np.testing.assert_array_equal(init, ko.kmeans_plusplus_init(X, 8, random_state=7))
 
 
-@pytest.mark.parametrize("n,d", [(8192 * 37 + 1234, 16), (8192 * 5, 5), (5000, 16), (8192 * 3 + 1, 20)])
-def test_seed_block_sums_and_scan_exact(ctx, n, d):
+# (n, d, family): every arm of the update's dispatcher (csrc/seed_update.hip
+# seed_update) at its smallest interesting shape — the compacted fp16 kernel
+# (d = 8, 16), the wide fp16 kernel (d = 32, 64; a one-row tail block, and a
+# single partial block: no full block at all), the plain kernel unrolled (d =
+# 5) and by runtime d (d = 20), and the fp64 kernel of F64 mode.
+_SEED_SUM_CASES = [(8192 * 37 + 1234, 16, "synth"), (8192 * 5, 5, "synth"), (5000, 16, "synth"),
+                   (8192 * 3 + 1, 20, "synth"), (8192 * 2 + 77, 8, "synth"),
+                   (8192 * 2 + 77, 32, "synth"), (8192 + 1, 64, "synth"), (3000, 64, "synth"),
+                   (8192 * 2 + 5, 5, "raw_f64")]
+
+
+@pytest.mark.parametrize(
+    "n,d,fam", _SEED_SUM_CASES,
+    ids=["%d-%d%s" % (n, d, "" if fam == "synth" else "-" + fam) for n, d, fam in _SEED_SUM_CASES])
+def test_seed_block_sums_and_scan_exact(ctx, n, d, fam):
     """Per-block D^2 sums are NumPy's pairwise add.reduce of each 8192 chunk,
     the total is dist_sq.sum(), and the device scan's last running value is
     np.cumsum(dist_sq / total)[-1] — all bit-exact (kmeans_plusplus.py:14-19)."""
     import _cdr
+    import data_families as df
 
-    X = synth.generate(n, 0, n, d, 8, 1000 + n + d)
+    if fam == "synth":
+        X = synth.generate(n, 0, n, d, 8, 1000 + n + d)
+    else:
+        X = df.family(fam, n, d, 1000 + n + d)
     ctx.load_points(X)
+    assert ctx.info()["mode"] == (df.MODE_F64 if fam == "raw_f64" else df.MODE_F32X)
     ctx.seed_reset()
     dist = np.full(n, np.inf)
     for c in (X[3], X[n // 2], X[n - 1]):
@@ -356,7 +374,7 @@ def test_f32x_gate_keeps_numpy_mean_exact(ctx):
 
 @pytest.mark.parametrize("n,outlier", [(8192 * 40 + 77, False), (8192 * 25, True), (3000, False)])
 def test_seed_program_cend_exact(ctx, n, outlier):
-    """The program scan (csrc/seed.hip seg_* kernels) fills the per-block
+    """The program scan (csrc/seed_scan.hip seg_* kernels) fills the per-block
     running values that seed_search reads: searchsorted(cumsum / c_last, u,
     'right') for u exactly at block ends and at random points equals NumPy's
     (kmeans_plusplus.py:19)."""
@@ -430,7 +448,7 @@ def test_seed_programs_compose_over_shards(ctx):
 @pytest.mark.parametrize("n,d,k", [(150_000, 64, 24), (150_000, 32, 24), (200_000, 8, 16),
                                    (120_000, 16, 40)])
 def test_seeding_fp16_certificate_vs_oracle(ctx, n, d, k):
-    """The fp16-certified seeding update (csrc/seed.hip seed_update16_kernel):
+    """The fp16-certified seeding update (csrc/seed_update.hip seed_update16c_kernel and seed_update16_kernel):
     minima it proves unchanged without the fp32 row must be exactly the ones
     the reference leaves unchanged — the seeds equal the reference run's,
     including with duplicated rows (zero distances, exact ties) and a far
@@ -445,7 +463,7 @@ def test_seeding_fp16_certificate_vs_oracle(ctx, n, d, k):
 
 
 def test_seeding_program_opaque_blocks(ctx):
-    """Blocks the cumsum program cannot summarise (csrc/seed.hip: more than
+    """Blocks the cumsum program cannot summarise (csrc/seed_scan.hip: more than
     32 binade crossings in a block -> FINE items walked element by element):
     a run of zero probabilities from a zero running value, and D^2 values
     growing 4x per row.  Seeds equal the reference's (kmeans_plusplus.py:

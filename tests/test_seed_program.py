@@ -2,7 +2,7 @@
 that sharded seeding uses to compose the shards' exact np.cumsum carries
 (src/kmeans_plusplus.py:19) instead of a rank-ordered chain.  Programs here
 come from tests/seedprog_model.py (the device builds them in
-csrc/seed.hip); the GPU side is tests/test_gpu_kmeans.py."""
+csrc/seed_scan.hip); the GPU side is tests/test_gpu_kmeans.py."""
 import numpy as np
 import pytest
 

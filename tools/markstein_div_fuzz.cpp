@@ -1,5 +1,5 @@
 // Host fuzz: fl(a / S) against Markstein's q0 = fl(a y), fl(q0 + fma(-q0, S, a) y), y = fl(1 / S)
-// (csrc/seed.hip seg_block_kernel).
+// (csrc/seed_scan.hip seg_block_kernel).
 //   g++ -O2 -ffp-contract=off -o /tmp/mk tools/markstein_div_fuzz.cpp
 //   /tmp/mk                      random significands (3.2e8 quotients)
 //   /tmp/mk midpoint [seed [n]]  quotients next to rounding midpoints (n draws, default 4e8)

@@ -1,4 +1,4 @@
-// Host fuzz: csrc/seed.hip part_add (int64 run counts) vs partd_add (fp64 integer counts + parity bits).
+// Host fuzz: csrc/seed_common.h part_add (int64 run counts) vs partd_add (fp64 integer counts + parity bits).
 // g++ -O2 -o /tmp/pd tools/partd_fuzz.cpp && /tmp/pd
 #include <cstdio>
 #include <cmath>
