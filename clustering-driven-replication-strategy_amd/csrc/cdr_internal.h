@@ -265,6 +265,10 @@ struct Ctx {
   int64_t ll_fin_count = 0;  // finalizes since lloyd_begin (2-byte rebase schedule)
   int32_t run_k = 0;
   bool last_delta = false;
+  // cdr_debug_screen (tests only): while it runs its step, the device buffer
+  // that receives every screen value; dbg_thr: that step's screen32 thresholds
+  float* dbg_vals = nullptr;
+  float dbg_thr[2] = {0.f, 0.f};
 #ifdef CDR_EXPERIMENTS
   int screen_ablate = 0;  // timing experiments only (never in the product build)
 #endif
@@ -435,15 +439,65 @@ void points_finish_resident(Ctx& c);
 void csv_index_count(Ctx& c, int64_t nb, long long* r8);
 void csv_index_write(Ctx& c, int64_t nb, int64_t nrec, bool tail);
 
+// ---- the Lloyd step (lloyd.hip and the files it hands the step to) ----
 void lloyd_step_f32x(Ctx& c, const double* C, int32_t k, int64_t* out,
                      bool out_on_device);
-void lloyd_step_f64(Ctx& c, const double* C, int32_t k, double* sums,
-                    int64_t* counts);
+int lloyd_num_cus(int device);  // CUs of the device (cached)
+void check_k(const Ctx& c, int k);
+void upload_centroids(Ctx& c, const double* C, int k);  // row-major fp64 -> c.cent64
+// The screens of lloyd_step_f32x, in its order.  Each returns false when it
+// does not take the shape, and then has launched nothing.
+// screen32.hip: d <= 16, k <= 64; C == nullptr: the device loop's plan
+bool screen32_supported(const Ctx& c, int k);
+bool screen32_step(Ctx& c, const double* C, int k, long long* dout, long long* hout, bool prof,
+                   float* dbg, float* thr_out, long long* gate);
+// screen_mid.hip: d <= 64, fragments + table within 64 KiB of LDS
+bool screen_supported(const Ctx& c, int k);
+bool mid_step(Ctx& c, const double* C, int k, long long* dout, bool prof);
+void mid_thresholds(const Ctx& c, const double* C, int k, float thr[2]);  // cdr_debug_screen
+// screen_big.hip: large k / d
+bool big_step(Ctx& c, const double* C, int k, long long* dout, bool prof);
+// test hooks (lloyd.hip's cdr_debug_* and layout entry points)
+void debug_plan32(Ctx& c, int which, const double* C, int k, float* out);  // screen32.hip
+void big_layout_read(Ctx& c, int64_t out[15]);                        // screen_big.hip
+int64_t debug_big_plan(Ctx& c, int k, void* out, int64_t bytes);     // screen_big.hip
+// lloyd_exact.hip: enqueue on the context stream.  Exact labels of every point
+// from c.cent64 (x32 or x64 by the mode); (k, d+1) int64 sums of the labels
+// into the zeroed dout; sum of c.partials' nwg tables (row stride KS) into
+// dout; cluster sizes of the labels into d_counts (zeroed here)
+void enqueue_assign_exact(Ctx& c, int k);
+void enqueue_update_from_labels(Ctx& c, int k, long long* dout);
+void enqueue_reduce_partials(Ctx& c, int nwg, int len, int KS, long long* dout);
+void enqueue_count_labels(Ctx& c, int k, long long* d_counts);
+// lloyd_f64.hip: c.f64x_walked = sum of f64x_walk's k*d counts (synchronises);
+// c.f64_sums and the device counts to the host, then read_walked or a
+// synchronise
+void read_walked(Ctx& c, int k);
+void copy_back_sums(Ctx& c, int k, const long long* d_counts, double* sums, int64_t* counts,
+                    bool walked);
+
+// Whatever decides labels without keeping the running state of the DELTA
+// screens (screen32's running sums and one-byte labels, the bounded screen's
+// bound words, the large-k running sums) drops all of it.
+inline void drop_running_state(Ctx& c) {
+  c.run_valid = false;
+  c.lab8_valid = false;
+  c.zb_valid = false;
+  c.big_valid = false;
+}
+
+// End of a step that wrote labels for k clusters; fallback: the points the
+// exact kernels decided (-1: unknown until cdr_lloyd_stats synchronises).
+inline void step_done(Ctx& c, int k, int64_t fallback) {
+  c.last_k = k;
+  c.have_labels = true;
+  c.med_k = 0;  // new labels: the grouped rows (medians.hip) are stale
+  c.last_fallback = fallback;
+}
 
 void seed_reset(Ctx& c);
 void seed_update(Ctx& c, const double* cent);
 void f32r_seed_update(Ctx& c, const float* cen, int reset, float* total);
-void lloyd_step_f32r(Ctx& c, const float* C, int32_t k, double* sums, int64_t* counts);
 bool f32_sums_parallel(Ctx& c, int k, double* d_sums);
 void seed_scan(Ctx& c, double total, double c_in, double* c_out);
 void events_ts_range(Ctx& c, int64_t ne);
@@ -500,13 +554,18 @@ void comm_release(Ctx& c);
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Profiling (lloyd.hip): prof_step_begin starts a profiled step when
+// Profiling (profile.hip): prof_step_begin starts a profiled step when
 // profiling is on (false otherwise); prof_mark(c, i) records event i of it
 // (0 start, 1 after the screen kernel, 2 end); prof_mark_sub(c) records the
 // end of the first of the screen's two kernels (split bounded screen).
+// prof_end_screened ends a profiled screened step whose fallback total sits
+// in fb_count: folds it into the profile, then the closing mark.  prof_drop
+// forgets the triple of a step that returns before its last event.
 bool prof_step_begin(Ctx& c);
 void prof_mark(Ctx& c, int i);
 void prof_mark_sub(Ctx& c);
+void prof_end_screened(Ctx& c);
+void prof_drop(Ctx& c);
 
 // The step's fallback total from the screens' per-wave counts fbc[0, nwaves)
 // (the DELTA screens write per-wave counts only: thousands of same-address

@@ -230,7 +230,7 @@ static void decide_mode(Ctx& c, const std::vector<unsigned long long>& st,
   }
   const long long need = (long long)st[2 * d] - 200000;
   int S = need < 0 ? 0 : (int)need;
-  // S <= 126: the kernels scale by 2^S as a float (lloyd.hip fx, screen32's
+  // S <= 126: the kernels scale by 2^S as a float (screen_mid.hip fx, screen32's
   // a.fx), finite only up to 2^127, and a grid step 2^-S below 2^-126 makes
   // the points fp32 subnormals; such data is F64 (tests/data_families.py tiny)
   bool f32x = (st[2 * d + 1] == 0) && S <= 126;
@@ -300,10 +300,7 @@ static void decide_mode(Ctx& c, const std::vector<unsigned long long>& st,
   c.have_labels = false;
   c.med_k = 0;  // (load, generate and restat all end here) the grouped rows are of other points
   c.gmed_begun = false;  // and so are the global medians' prefixes
-  c.run_valid = false;
-  c.lab8_valid = false;
-  c.zb_valid = false;
-  c.big_valid = false;
+  drop_running_state(c);
   for (int64_t& v : c.big_info) v = 0;  // no large-k step on these points yet
   c.seed_scanned = false;
 }
@@ -331,9 +328,7 @@ static void reset_points(Ctx& c, int64_t n, int32_t d) {
   c.n = n;
   c.d = d;
   c.n_pad = ceil_div(n > 0 ? n : 1, kSeedBlock) * kSeedBlock;
-  c.run_valid = false;
-  c.lab8_valid = false;
-  c.zb_valid = false;
+  drop_running_state(c);
   c.ll_on = false;
   c.med_k = 0;
   c.gmed_begun = false;

@@ -36,8 +36,6 @@
 
 namespace cdr {
 
-int lloyd_num_cus(int device);
-
 namespace {
 
 constexpr int kGbTile = 8192;                   // events per partition tile
@@ -1334,14 +1332,6 @@ __global__ __launch_bounds__(kGbBThreads) void gb_bucket_big(
   }
   __syncthreads();
   gb_write_files(g, nfl, f0, out);
-}
-
-// forget the profile triple of a step that returns before its last event
-void prof_drop(Ctx& c) {
-  if (c.prof_cur >= 0) {
-    c.prof_used -= 4;
-    c.prof_cur = -1;
-  }
 }
 
 int bitlen(unsigned long long v) {  // bits to hold v (0 -> 0)

@@ -37,11 +37,7 @@ namespace cdr {
 
 constexpr int kLLState = 8;  // int64 words of ll_state
 
-bool screen32_supported(const Ctx& c, int k);
-bool screen32_step(Ctx& c, const double* C, int k, long long* dout, long long* hout, bool prof,
-                   float* dbg, float* thr_out, long long* gate);
 void plan32_point_side(const Ctx& c, double& xxmax, double& l1x);
-void lloyd_step_f32x(Ctx& c, const double* C, int32_t k, int64_t* out, bool out_dev);
 void zh_rebase(Ctx& c, const long long* gate);  // screen32b.hip
 constexpr int kRebaseEvery = 4;  // finalizes between 2-byte rebase opportunities
 
@@ -263,7 +259,6 @@ void plan32_launch(Ctx& c, int k, int QH, int MT);  // screen32.hip
 bool big_supported(const Ctx& c, int k);              // screen_big.hip
 void big_plan_device(Ctx& c, int k, const double* dC, const double* dmu, const long long* gate);
 bool big_step_dev(Ctx& c, int k, long long* dout, bool prof, const long long* gate);
-void prof_end_screened(Ctx& c);                       // lloyd.hip
 
 // Large-k plan of the loop's current centroids (begin, resume, and after
 // each finalize that moved them); ll_ref + d holds mu as fp64.
@@ -354,10 +349,7 @@ int cdr_lloyd_begin(cdr_ctx* h, const double* C, int32_t k, double tol, int32_t 
   c.ll_fin_count = 0;
   c.ll_hostplan_once = false;
   // the first step recomputes the running sums from scratch (see resume)
-  c.run_valid = false;
-  c.lab8_valid = false;
-  c.zb_valid = false;
-  c.big_valid = false;
+  drop_running_state(c);
   if (c.ll_devplan) ll_plan(c);
   if (c.ll_devbig) ll_plan_big(c);
   CDR_CATCH
@@ -607,10 +599,7 @@ int cdr_lloyd_resume(cdr_ctx* h, const double* C, int32_t add_steps, int32_t hos
   // Steps enqueued after the stop did nothing, but the host marked the
   // running sums valid after each of them; a full (non-DELTA) step that was
   // among them never zeroed and rebuilt them.  The next step starts afresh.
-  c.run_valid = false;
-  c.lab8_valid = false;
-  c.zb_valid = false;
-  c.big_valid = false;
+  drop_running_state(c);
   CDR_CATCH
 }
 

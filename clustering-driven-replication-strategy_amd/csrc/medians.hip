@@ -733,8 +733,6 @@ __global__ __launch_bounds__(kGmThreads) void gm_hist64(const double* __restrict
   }
 }
 
-int lloyd_num_cus(int device);
-
 static void gm_need_points(const Ctx& c) {
   if (c.mode != CDR_MODE_F32X && c.mode != CDR_MODE_F64)
     CDR_FAIL(CDR_ERR_STATE, "global medians: no points loaded");

@@ -142,8 +142,6 @@ struct Plan32 {
   std::vector<float> prune;  // the prune block (plan32.h: c32 | E | h)
 };
 
-extern int lloyd_num_cus(int device);
-
 // dst[i] = src[i] for 16-byte words; src is mapped pinned host memory.
 __global__ __launch_bounds__(256) void pull_host_kernel(const uint4* __restrict__ src,
                                                         uint4* __restrict__ dst, int64_t n16) {

@@ -1114,7 +1114,6 @@ __global__ __launch_bounds__(1024) void fixup_big(const float* __restrict__ XA, 
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-extern int lloyd_num_cus(int device);
 void ensure_precentered(Ctx& c);
 void ensure_rowmajor(Ctx& c);
 
@@ -1652,11 +1651,9 @@ static bool big_launch(Ctx& c, int k, float thr1, float thr_rel, const float* th
   }
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(dout, bs, sizeof(long long) * len, hipMemcpyDeviceToDevice, c.stream));
+  drop_running_state(c);  // the large-k running sums are the only ones that follow these labels
   c.big_valid = true;
   c.big_k = k;
-  c.run_valid = false;
-  c.lab8_valid = false;
-  c.zb_valid = false;
   return true;
 }
 

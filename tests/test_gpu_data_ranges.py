@@ -33,7 +33,7 @@ def _expected_kernel(name, d, k, want):
         full = "true" if q4 == 2 * qh else "false"
         return ("screen32<%d,%d,%s,false,false,%s>" % (qh, mt, full, pre),)
     kt, dch = (k + 15) // 16, (d + 15) // 16
-    if k * (d + 1) * 8 + kt * dch * 2 * 64 * 16 <= 64 * 1024:  # the host-plan screens (lloyd.hip)
+    if k * (d + 1) * 8 + kt * dch * 2 * 64 * 16 <= 64 * 1024:  # the host-plan screens (screen_mid.hip)
         return ("screen_fast<%d,%d>" % (dch, kt) if kt * dch <= 4 else "screen_kernel<%d>" % dch,)
     if want[2]:
         return ("screen_big",)

@@ -125,8 +125,8 @@ def test_delta_invalidation(ctx):
         np.testing.assert_array_equal(ctx.labels(), lab)
         np.testing.assert_array_equal(out, want)
         if delta is None:
-            # the small-k screen of lloyd.hip (screen_kernel<2> at this shape; its
-            # branch, shared with screen_fast, drops the large-k running sums)
+            # the small-k screen of screen_mid.hip (screen_kernel<2> at this shape; its
+            # step (mid_step), shared with screen_fast, drops the large-k running sums)
             assert ctx.profile_kernel().startswith(("screen_kernel", "screen_fast"))
         else:
             _check_form(ctx, d, k, delta)

@@ -1,5 +1,5 @@
 """In-process A/B timing of the general screen (screen_kernel / screen_fast in
-csrc/lloyd.hip: the shapes outside screen32 and screen_big, by default
+csrc/screen_mid.hip: the shapes outside screen32 and screen_big, by default
 d = 24, k = 33) with parts switched off through cdr_debug_screen_ablate
 (interleaved rounds, HIP-event timings).  The small-shape screens
 (csrc/screen32*.hip) have no ablation arms.  Diagnostic tool, not a test.
