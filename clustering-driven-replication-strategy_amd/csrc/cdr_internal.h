@@ -185,11 +185,7 @@ struct Ctx {
   DevBuf f64r_state, f64r_keep;
   // f64sum.hip: block sums, counts, predicted binades, transfers, walk counts
   DevBuf f64x_A, f64x_cnt, f64x_E, f64x_T, f64x_walk, f64x_G, f64x_GS, f64x_prof;
-  // f64_step_fused: the binade predictions of the last F64 step (two buffers:
-  // the one the current transfers use, the next step's), valid for (k, blocks)
-  DevBuf f64x_E2;
   DevBuf f64x_GC;  // f64_step_fused: per (cluster, group of 64 blocks) member counts
-  DevBuf f64x_ord;  // f64_step_fused: each block's rows in cluster order (uint8 offsets)
   DevBuf f64x_cs;   // f64_cent_prep: the screen's fp32 centroid rows + norms, then its ok flag
   // f64_step_fused's transfer cache (cdr_lloyd_f64_run): per block {labels
   // changed this step, step stamp of its last binade change}, the list of the
@@ -198,9 +194,6 @@ struct Ctx {
   int f64x_stamp = 0;
   DevBuf f64s_off;  // sharded F64 sums: earlier shards' approximate totals, end binades
   int32_t f64s_k = 0, f64s_nranks = 0, f64s_rank = 0;  // cdr_f64s_begin's step
-  bool f64x_e_ok = false;
-  int f64x_e_cur = 0, f64x_e_k = 0;
-  int64_t f64x_e_nb = 0;
   int64_t f64x_walked = -1;  // blocks re-added element-wise in the last F64 step (-1: serial)
   HostBuf h_small;  // pinned scratch for small D2H
   HostBuf h_up;     // pinned staging of the per-step screen32 upload
@@ -521,21 +514,22 @@ void features_aggregate(Ctx& c, int64_t n_events, const int32_t* file_idx,
 bool groupby_resident(Ctx& c, int64_t ne, int64_t nf, int64_t* out, int64_t* max_ts);
 // exact sequential-order F64 centroid sums in parallel (f64sum.hip); false =
 // shape not covered (d < 2 or k > 64)
-bool f64_sums_parallel(Ctx& c, int k, double* d_sums, bool pre = false);
+bool f64_sums_parallel(Ctx& c, int k, double* d_sums);
 // stable LSD radix sort of (key, value) pairs over key bits [0, end_bit)
 // (radix.hip); true when the sorted pairs are in (k1, v1)
 template <typename K, typename V>
 bool radix_sort_pairs(Ctx& c, K* k0, K* k1, V* v0, V* v1, int64_t n, int end_bit);
-// sharded F64 sums (f64sum.hip; include/cdr.h cdr_f64s_*)
+// sharded F64 sums (f64_sharded.hip; include/cdr.h cdr_f64s_*)
 int f64s_cap();
 bool f64s_assign_totals(Ctx& c, int k, const double* dC, double* tot_slot);
 void f64s_build(Ctx& c, int k, int nranks, int rank, const double* tot_all, void* prog_all);
 void f64s_compose_all(Ctx& c, int k, int nranks, const double* tot_all, const void* prog_all,
                       double* d_sums, long long* d_counts, int* d_status);
 void f64s_chain_walk(Ctx& c, int k, double* chain);
-// tcache: 0 every transfer formed; 1 every transfer formed and the cache
-// started; 2 only the blocks whose labels or binade predictions changed since
-// the previous tcache step (the others keep their transfers)
+// the fused F64 step (f64_assign.hip).  tcache: 0 every transfer formed; 1
+// every transfer formed and the cache started; 2 only the blocks whose labels
+// or binade predictions changed since the previous tcache step (the others
+// keep their transfers)
 bool f64_step_fused(Ctx& c, int k, const double* dC, double* d_sums,
                     unsigned long long* d_counts, bool prof, const long long* gate = nullptr,
                     int tcache = 0);

@@ -3,7 +3,8 @@
 // feature) — NumPy's X[mask].mean(axis=0) is a sequential row-order sum for
 // d >= 2 and the blocked pairwise sum for d == 1 (oracle/kmeans_oracle.py
 // pins both against NumPy); the device-resident F64 run and the sharded F64
-// sums' entry points (their other kernels: f64sum.hip, lloyd_exact.hip).
+// sums' entry points (their other kernels: f64sum.hip, f64_assign.hip,
+// f64_sharded.hip, lloyd_exact.hip).
 #include <cstdio>
 #include <cmath>
 
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(kF64RunThreads) void f64_run_update(
   }
 }
 
-// cdr_lloyd_f64_run: up to max_steps fused F64 steps (f64sum.hip) with the
+// cdr_lloyd_f64_run: up to max_steps fused F64 steps (f64_assign.hip) with the
 // update above on the device; one synchronisation at the end.
 static void lloyd_run_f64(Ctx& c, const double* C, int32_t k, int32_t max_steps, double tol,
                           double* C_out, double* means_out, int64_t* counts_out, int32_t* info) {
@@ -209,8 +210,8 @@ static void lloyd_step_f64(Ctx& c, const double* C, int32_t k, double* sums, int
   c.f64_sums.ensure(sizeof(double) * (size_t)k * d);
   c.f64_counts.ensure(sizeof(long long) * k * 2);
   long long* cnt_pre = c.f64_counts.as<long long>() + k;
-  // the fused pipeline (f64sum.hip: assignment + block pass, transfers from
-  // the previous step's binade predictions; CDR_F64_FUSE=0: separate passes)
+  // the fused pipeline (f64_assign.hip: assignment + block pass, then the
+  // sums of f64sum.hip; CDR_F64_FUSE=0: separate passes)
   static const bool fuse_env = !exp_env("CDR_F64_FUSE") || atoi(exp_env("CDR_F64_FUSE"));
   if (fuse_env && !getenv("CDR_F64_SERIAL")) {
     snprintf(c.prof_kernel, sizeof(c.prof_kernel), "f64_assign_block<%d>", d);
@@ -280,7 +281,7 @@ int cdr_lloyd_f64_walked(cdr_ctx* h, int64_t* walked) {
   CDR_CATCH
 }
 
-// ---- sharded F64 sums (f64sum.hip, include/cdr.h cdr_f64s_*) ----
+// ---- sharded F64 sums (f64_sharded.hip, include/cdr.h cdr_f64s_*) ----
 int cdr_f64s_begin(cdr_ctx* h, const double* C, int32_t k, int32_t nranks, int32_t rank,
                    void* tot_buf, int64_t* sizes) {
   CDR_TRY

@@ -1,5 +1,5 @@
 """Python model of the sharded F64 sums (include/cdr.h cdr_f64s_*,
-csrc/f64sum.hip f64s_program / f64s_compose) for the CPU tests: a shard's
+csrc/f64_sharded.hip f64s_program / f64s_compose) for the CPU tests: a shard's
 part of every (cluster, feature) sequence as a program of RUN transfers
 (member blocks predicted in one binade, no crossing inside) and ELEM values
 (every other member), composed in rank order from the exact start.  Test
