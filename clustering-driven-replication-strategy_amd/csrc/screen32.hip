@@ -468,6 +468,22 @@ static void s32bs_tprof_report(Ctx& c, const unsigned long long* tprof_buf, int 
 }
 #endif
 
+// The watch list's switches that do not depend on the grid:
+// 2-byte words of the fused screen32bs (z16), not with every bound failing
+// (dbg: CDR_BOUNDS_DBG), from kS32WatchMinPts padded points (tests:
+// CDR_S32BS_WATCH_MIN); CDR_S32BS_WATCH=0: off.  Read on every call.
+static bool s32_watch_wanted(const Ctx& c, bool z16, int dbg) {
+  if (!z16 || (dbg & 1)) return false;
+  if (const char* e = std::getenv("CDR_S32BS_WATCH"))
+    if (std::atoi(e) == 0) return false;
+  int64_t wmin = kS32WatchMinPts;
+  if (const char* e = std::getenv("CDR_S32BS_WATCH_MIN")) {
+    const long long v = std::atoll(e);
+    if (v >= 1) wmin = v;
+  }
+  return c.n_pad >= wmin;
+}
+
 // A DELTA step (labels and running sums as the full screen's): the pruned
 // screen, or in the device loop, where ll_finalize32 keeps the drift bounds of
 // every centroid move, a bounded screen: screen32bs in its fused 2-byte form
@@ -498,8 +514,22 @@ static void screen32_delta_step(Ctx& c, int QH, int MT, int k, const h8* dfrag,
     if (v >= 8 && v % 8 == 0 && v <= cus) cus = v;
   }
   int bpc;
+  // (the list path launches screen32bsw; whether the waves' ranges fit the
+  // list is known only with the grid, so that grid fits both kernels)
+  // (the switches of the bounded launch below, read once here: the split form
+  // CDR_S32BS_SPLIT=1 and 2-byte words otherwise; CDR_BOUNDS_DBG, a test
+  // switch whose bit 0 makes every bound fail)
+  const bool split_env =
+      BS && std::getenv("CDR_S32BS_SPLIT") && std::atoi(std::getenv("CDR_S32BS_SPLIT"));
+  const bool z16 = BS && !split_env;
+  int bdbg = std::getenv("CDR_BOUNDS_DBG") ? std::atoi(std::getenv("CDR_BOUNDS_DBG")) : 0;
+#ifndef CDR_EXPERIMENTS
+  bdbg &= 1;  // (the other bits are timing experiments: experiments build only)
+#endif
+  const bool watch_wanted = s32_watch_wanted(c, z16, bdbg);
   if (BS) {
-    bpc = screen32bs_blocks_per_cu(Q, MT);
+    bpc = screen32bs_blocks_per_cu(Q, MT, false);
+    if (watch_wanted) bpc = std::min(bpc, screen32bs_blocks_per_cu(Q, MT, true));
     // (experiments: fewer workgroups per CU, CDR_S32BS_BPC=1..3)
     static const int bsb_env = exp_env("CDR_S32BS_BPC") ? std::atoi(exp_env("CDR_S32BS_BPC")) : 0;
     if (bsb_env >= 1 && bsb_env < bpc) bpc = bsb_env;
@@ -604,9 +634,6 @@ static void screen32_delta_step(Ctx& c, int QH, int MT, int k, const h8* dfrag,
     // first bounded step of a run; the row-major hi copy (screen32b) once
     // per point set.  The fused screen32bs keeps 2-byte words (DESIGN.md
     // 4.3g); the split form (CDR_S32BS_SPLIT=1) and screen32b 4-byte ones
-    const bool split_env =
-        BS && std::getenv("CDR_S32BS_SPLIT") && std::atoi(std::getenv("CDR_S32BS_SPLIT"));
-    const bool z16 = BS && !split_env;
     const int zfmt = z16 ? 16 : 32;
     if (c.zb_fmt != zfmt) c.zb_valid = false;
     c.zb_fmt = zfmt;
@@ -645,11 +672,7 @@ static void screen32_delta_step(Ctx& c, int QH, int MT, int k, const h8* dfrag,
     b.zh = z16 ? c.zb.as<uint16_t>() : nullptr;
     b.bt = reinterpret_cast<const unsigned char*>(c.bnd.p);
     b.t_acc = c.prof_on ? c.t_acc.as<long long>() : nullptr;
-    // (a test switch, read on every call: bit 0 makes every bound fail)
-    b.dbg = std::getenv("CDR_BOUNDS_DBG") ? std::atoi(std::getenv("CDR_BOUNDS_DBG")) : 0;
-#ifndef CDR_EXPERIMENTS
-    b.dbg &= 1;  // (the other bits are timing experiments: experiments build only)
-#endif
+    b.dbg = bdbg;
     // screen32bs's direct test; CDR_S32BS_DIRECT=0 (tests, A/B):
     // the triangle test and the split screen decide, read on every call
     b.direct = !std::getenv("CDR_S32BS_DIRECT") || std::atoi(std::getenv("CDR_S32BS_DIRECT"));
@@ -738,25 +761,18 @@ static void screen32_delta_step(Ctx& c, int QH, int MT, int k, const h8* dfrag,
           (z16 ? kZ16Chunk : kBChunk);
       // The watch list: wave w of this grid keeps the points [w wrange,
       // (w + 1) wrange) in a region of wcap entries.  On for 2-byte words from
-      // kS32WatchMinPts padded points (tests: CDR_S32BS_WATCH_MIN) while the
-      // range fits the entries' 16-bit offset; CDR_S32BS_WATCH=0: off.  The
+      // kS32WatchMinPts padded points (s32_watch_wanted) while the
+      // range fits the entries' 16-bit offset.  The
       // capacity is half the range: a longer list (4 bytes an entry) streams
       // more bytes than the words (2 bytes a point), and the largest list of
       // the beta sweep at config 3 stayed far below it (tests:
-      // CDR_S32BS_WATCH_CAP entries, up to the range).  All read on every call.
+      // CDR_S32BS_WATCH_CAP entries, up to the range; read on every call).
       b.watch = nullptr;
       b.wl = nullptr;
       b.wn = b.wf = nullptr;
       b.wcap = b.wrange = 0;
-      bool watch = z16 && !(b.dbg & 1);
-      if (const char* e = std::getenv("CDR_S32BS_WATCH")) watch = watch && std::atoi(e) != 0;
-      int64_t wmin = kS32WatchMinPts;
-      if (const char* e = std::getenv("CDR_S32BS_WATCH_MIN")) {
-        const long long v = std::atoll(e);
-        if (v >= 1) wmin = v;
-      }
       const int64_t wrange = ceil_div(b.nchunks, (int64_t)nwaves) * kZ16Chunk;
-      watch = watch && c.n_pad >= wmin && wrange <= kS32WatchMaxRange;
+      const bool watch = watch_wanted && wrange <= kS32WatchMaxRange;
       if (watch) {
         int64_t wcap = ceil_div(wrange / 2, (int64_t)256) * 256;
         if (const char* e = std::getenv("CDR_S32BS_WATCH_CAP")) {
@@ -813,8 +829,8 @@ static void screen32_delta_step(Ctx& c, int QH, int MT, int k, const h8* dfrag,
         screen32bz_launch(grid, c.stream, b);
         if (prof) prof_mark_sub(c);
       }
-      // (the list path: both forms, each gated on the mode word; one exits at once)
-      if (b.watch) screen32bs_watch_launch(Q, MT, grid, c.stream, b);
+      // (the list path, b.watch: one launch, the mode word picks the form;
+      // <4,1>: a launch per form, each gated on the mode word)
       screen32bs_launch(Q, MT, grid, c.stream, b, split_env);
 #ifdef CDR_EXPERIMENTS
       if (tprof_on) s32bs_tprof_report(c, tprof_buf, nwaves, split_env);

@@ -370,10 +370,11 @@ void screen32bz_launch(dim3 grid, hipStream_t s, const S32BArgs& p);
 void bound_words_reset(bool z16, hipStream_t s, const uint8_t* lab8, void* zb, int64_t n,
                        int64_t n_pad, const long long* gate);
 void zh_rebase(Ctx& c, const long long* gate);
-// screen32bs.hip: screen32bs<Q, MT, split> (split: the lists of screen32bz)
-int screen32bs_blocks_per_cu(int Q, int MT);
+// screen32bs.hip: screen32bs<Q, MT, split> (split: the lists of screen32bz),
+// or with a watch list in the arguments (p.watch; list: its occupancy)
+// screen32bsw<Q, MT>, one launch running the default or the WATCH form
+// (<4,1>: the two forms' own kernels, each gated on the mode word)
+int screen32bs_blocks_per_cu(int Q, int MT, bool list);
 void screen32bs_launch(int Q, int MT, dim3 grid, hipStream_t s, const S32BArgs& p, bool split);
-// ... and its WATCH form on the same grid (both gate on the mode word)
-void screen32bs_watch_launch(int Q, int MT, dim3 grid, hipStream_t s, const S32BArgs& p);
 
 }  // namespace cdr
