@@ -162,6 +162,10 @@ SIGNATURES = {
     "cdr_plan_bound": ([_I64, _I64, _PI64], None),
     "cdr_plan_timing": ([_P, _P], None),
     "cdr_plan_size_sums": ([_P, _P, _I64, _I32, _P, _P], None),
+    "cdr_agree_keep": ([_P], None),
+    "cdr_agree_table": ([_P, _P, _I32, _P, _I32, _I64, _P, _P, _P], None),
+    "cdr_agree_info": ([_P, _P], None),
+    "cdr_agree_timing": ([_P, _P], None),
     "cdr_host_seq_sum": ([_P, _I64, _F64], ctypes.c_double),
 }
 
@@ -1231,6 +1235,56 @@ class Context:
                                             _ptr(sizes) if sizes is not None and n else None,
                                             _ptr(out)))
         return [int(out[j, 0]) + (int(out[j, 1]) << 32) for j in range(int(k))]
+
+    # -- two clusterings compared on the device (csrc/agree.hip) -------------
+    def agree_keep(self) -> None:
+        """Keeps a device copy of the resident labels (cdr_agree_keep): the `b`
+        side of later ``agree_table(labels_b=None)`` calls, whatever Lloyd
+        steps or ``load_points`` follow."""
+        _check(self._lib.cdr_agree_keep(self._h))
+
+    def agree_table(self, ka: int, kb: int, labels_a=None, labels_b=None, sizes=None):
+        """The contingency table of two labelings of the same rows
+        (cdr_agree_table): counts int64 (ka, kb).  labels_a None: the resident
+        labels; labels_b None: the kept ones (``agree_keep``).  With `sizes`
+        (int64 >= 0, one per row) returns ``(counts, bytes)``, bytes an object
+        array (ka, kb) of exact Python ints."""
+        la = None if labels_a is None else np.ascontiguousarray(labels_a, dtype=np.int64).ravel()
+        lb = None if labels_b is None else np.ascontiguousarray(labels_b, dtype=np.int64).ravel()
+        if sizes is not None:
+            sizes = np.ascontiguousarray(sizes, dtype=np.int64).ravel()
+        given = [v.size for v in (la, lb, sizes) if v is not None]
+        if len(set(given)) > 1:
+            raise ValueError(f"labels_a, labels_b and sizes differ in length: {given}")
+        n = given[0] if given else self.info()["n"]
+        ka, kb = int(ka), int(kb)
+        shape = (min(max(ka, 1), 1024), min(max(kb, 1), 1024))  # (a k out of range: the library's error)
+        counts = np.zeros(shape, dtype=np.uint64)
+        sums = np.zeros(shape + (2,), dtype=np.uint64) if sizes is not None else None
+        _check(self._lib.cdr_agree_table(
+            self._h, None if la is None else _ptr(la), ka, None if lb is None else _ptr(lb), kb, n,
+            None if sizes is None else _ptr(sizes), _ptr(counts),
+            None if sums is None else _ptr(sums)))
+        counts = counts.astype(np.int64)
+        if sums is None:
+            return counts
+        # lo + (hi << 32) in Python ints (object arrays): the total can pass uint64
+        return counts, sums[..., 0].astype(object) + sums[..., 1].astype(object) * (1 << 32)
+
+    def agree_info(self) -> dict:
+        """cdr_agree_info: ``form`` of the last agree_table (0 LDS, 1 global, -1
+        none yet), the LDS form's cell caps ``cap_counts`` / ``cap_sizes`` and
+        the ``workgroups`` of the last launch."""
+        out = np.zeros(4, dtype=np.int64)
+        _check(self._lib.cdr_agree_info(self._h, _ptr(out)))
+        return {"form": int(out[0]), "cap_counts": int(out[1]), "cap_sizes": int(out[2]),
+                "workgroups": int(out[3])}
+
+    def agree_timing(self) -> np.ndarray:
+        """{uploads, kernel, copy back} ms of the last agree_table."""
+        out = np.zeros(3, dtype=np.float64)
+        _check(self._lib.cdr_agree_timing(self._h, _ptr(out)))
+        return out
 
 
 def _pack_strings(strs):

@@ -31,7 +31,7 @@ import numpy as np
 import kmeans_plusplus as _kp
 from _cdr import Context, default_context
 
-__all__ = ["silhouette", "davies_bouldin", "sweep", "DEFAULT_SAMPLE"]
+__all__ = ["silhouette", "davies_bouldin", "sweep", "stability", "DEFAULT_SAMPLE"]
 
 DEFAULT_SAMPLE = 65536  # rows of the default silhouette sample (4.3e9 pairs)
 
@@ -150,3 +150,31 @@ def sweep(X, ks, *, random_state=None, max_iter=None, sample_size=None,
         rows.append({"k": k, "inertia": ctx.last_inertia, "silhouette": sil,
                      "davies_bouldin": db, "nonempty": nonempty})
     return rows
+
+
+def stability(X, k, random_states, *, max_iter=None, context: Context | None = None,
+              comm=None) -> dict:
+    """Whether k gives the same partition from different seeds: ``kmeans`` with
+    every seed of random_states (at least 2) on one load of X, and the adjusted
+    Rand index of each further run against the first.  The first run's labels
+    are kept on the device (``cluster_agreement.keep``) and every comparison is
+    one contingency table of the resident against the kept labels
+    (``cluster_agreement.contingency``): the comparison moves no label array to
+    the host (each ``kmeans`` run itself still returns its labels, as in ``sweep``).
+    Returns ``{"k", "ari": [one per further seed], "mean", "min"}``."""
+    import cluster_agreement as _ca
+
+    X = np.asarray(X)
+    seeds = list(random_states)
+    if len(seeds) < 2:
+        raise ValueError("stability needs at least 2 random states")
+    ctx = _context(X, context, comm)
+    k = int(k)
+    ari = []
+    for j, seed in enumerate(seeds):
+        _kp._kmeans_loaded(ctx, X, k, 100, 1e-4, seed, max_iter)
+        if j == 0:
+            _ca.keep(context=ctx)
+        else:
+            ari.append(_ca.adjusted_rand(_ca.contingency(ka=k, kb=k, context=ctx)))
+    return {"k": k, "ari": ari, "mean": float(np.mean(ari)), "min": float(min(ari))}

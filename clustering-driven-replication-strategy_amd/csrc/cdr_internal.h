@@ -364,6 +364,18 @@ struct Ctx {
   int32_t plan_k = 0;
   bool plan_resident = false;
   double plan_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  // agree.hip: the labels cdr_agree_keep copied (int32, their row count, -1:
+  // none, and their k; nothing but another keep replaces them), explicit
+  // labels of either side as int32 and their pinned staging, the sizes, the
+  // table {counts, sums, flag} and its pinned copy; the last call's form (0
+  // LDS, 1 global, -1: none yet), its workgroups and {uploads, kernel, copy
+  // back} ms
+  DevBuf agree_kept, agree_a, agree_b, agree_sz, agree_tab;
+  HostBuf agree_stage, agree_host;
+  int64_t agree_kept_n = -1;
+  int32_t agree_kept_k = 0;
+  int64_t agree_form = -1, agree_wgs = 0;
+  double agree_ms[3] = {0.0, 0.0, 0.0};
   // clusters of the grouped rows (cdr_medians_group); 0 = none: whatever
   // replaces the points, rewrites the labels or reuses med_vals / med_off /
   // med_out (medians_segmented) clears it, and the pass entries refuse to run.

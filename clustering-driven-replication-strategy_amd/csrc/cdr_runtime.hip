@@ -471,8 +471,11 @@ int cdr_destroy(cdr_ctx* h) {
                     &c.cin_bytes, &c.cin_tile, &c.cin_part, &c.cin_mask, &c.cin_ends, &c.cin_sc,
                     &c.cin_blk, &c.cin_cnt, &c.cin_map, &c.cin_def,
                     &c.plan_lab, &c.plan_tails, &c.plan_fstart, &c.plan_flen, &c.plan_rowoff,
-                    &c.plan_part, &c.plan_def, &c.plan_out, &c.plan_sz, &c.plan_sum};
+                    &c.plan_part, &c.plan_def, &c.plan_out, &c.plan_sz, &c.plan_sum,
+                    &c.agree_kept, &c.agree_a, &c.agree_b, &c.agree_sz, &c.agree_tab};
   for (DevBuf* b : bufs) b->release();
+  c.agree_stage.release();
+  c.agree_host.release();
   c.h_small.release();
   c.h_up.release();
   c.csv_host.release();

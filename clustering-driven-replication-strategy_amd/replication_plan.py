@@ -27,6 +27,14 @@ CLI (the join of ``size_bytes`` on ``path`` for ``--manifest`` is host work, pan
 
     python replication_plan.py --input_path F --k K --tables T.json --out plan.csv
                                [--manifest M.csv] [--current_factor R]
+                               [--previous_plan PREV.csv]
+
+From the second plan on each file already carries the previous plan's factor,
+so what a new plan costs is summed per file against that: ``transition`` (the
+moves between the categories of two plans) from the contingency table of the
+two clusterings (csrc/agree.hip, cluster_agreement.py), weighted by the sizes.
+``--previous_plan`` (a file this module wrote; joined on ``path`` by pandas)
+prints it as one more JSON line after ``summarize``'s.
 """
 from __future__ import annotations
 
@@ -43,7 +51,8 @@ import numpy as np
 
 from _cdr import PLAN_MAX_TAIL, Context, default_context
 
-__all__ = ["HEADER", "write_plan_csv", "write_plan_csv_host", "summarize", "main"]
+__all__ = ["HEADER", "write_plan_csv", "write_plan_csv_host", "summarize", "transition",
+           "transition_from_table", "main"]
 
 HEADER = ["path", "cluster", "category", "replication"]
 MAX_K = 1024                  # cdr_plan_format's k
@@ -320,6 +329,112 @@ def summarize(categories, replication_factors, k, *, sizes=None, current_factor=
     return {"categories": out, "total": total}
 
 
+def transition_from_table(counts, nbytes, prev_cats, prev_facs, cats, facs) -> dict:
+    """What a new plan changes against the previous one, from the contingency
+    table of the two clusterings: ``counts[i][j]`` files (and ``nbytes[i][j]``
+    bytes, or None) that were in previous cluster i and are in new cluster j;
+    ``prev_cats`` / ``prev_facs`` the category and factor of previous cluster i,
+    ``cats`` / ``facs`` of new cluster j.  Returns ``{"moves": {old_category:
+    {new_category: {...}}}, "total": {...}}``: per pair of categories that holds
+    files ``old_factor``, ``new_factor``, ``files`` and with bytes also
+    ``bytes``, ``bytes_to_copy = max(new - old, 0) * bytes`` and
+    ``bytes_to_free = max(old - new, 0) * bytes``; ``total`` sums them and adds
+    ``files_changed``, the files whose factor differs.  Arithmetic on Python
+    ints; a category with two factors on one side is a ValueError."""
+    ka, kb = len(prev_cats), len(cats)
+    if len(prev_facs) != ka or len(facs) != kb:
+        raise ValueError("one factor per cluster")
+    counts = np.asarray(counts)
+    if counts.shape != (ka, kb):
+        raise ValueError(f"the table is {counts.shape}, the clusterings have {ka} and {kb} clusters")
+    if nbytes is not None:
+        nbytes = np.asarray(nbytes, dtype=object)
+        if nbytes.shape != (ka, kb):
+            raise ValueError(f"the byte table is {nbytes.shape}, not {(ka, kb)}")
+    keys = ["files"] + (["bytes", "bytes_to_copy", "bytes_to_free"] if nbytes is not None else [])
+    moves = {}
+    total = dict({key: 0 for key in keys}, files_changed=0)
+    for i in range(ka):
+        for j in range(kb):
+            files = int(counts[i, j])
+            if files == 0:
+                continue
+            old, new = int(prev_facs[i]), int(facs[j])
+            row = moves.setdefault(prev_cats[i], {}).setdefault(
+                cats[j], dict({"old_factor": old, "new_factor": new}, **{key: 0 for key in keys}))
+            if (row["old_factor"], row["new_factor"]) != (old, new):
+                raise ValueError(f"the move {prev_cats[i]!r} -> {cats[j]!r} has two pairs of factors")
+            add = {"files": files}
+            if nbytes is not None:
+                b = int(nbytes[i, j])
+                add.update(bytes=b, bytes_to_copy=max(new - old, 0) * b,
+                           bytes_to_free=max(old - new, 0) * b)
+            for key, v in add.items():
+                row[key] += v
+                total[key] += v
+            if old != new:
+                total["files_changed"] += files
+    return {"moves": moves, "total": total}
+
+
+def transition(prev_categories, prev_replication_factors, prev_k, categories, replication_factors,
+               k, *, prev_labels=None, labels=None, sizes=None, context: Context | None = None,
+               prefix="C") -> dict:
+    """``transition_from_table`` of the previous plan (its category and factor
+    tables and its k) and the new one.  ``prev_labels=None``: the labels kept on
+    the device (``cluster_agreement.keep``); ``labels=None``: the labels
+    resident in ``context``; ``sizes``: int64 >= 0, one per file.  Both pairs of
+    tables are validated as ``summarize`` validates its own; the table comes
+    from one cdr_agree_table call over all files."""
+    ctx = context if context is not None else default_context()
+    prev_k, k = int(prev_k), int(k)
+    prev_cats, prev_facs = _tables(prev_categories, prev_replication_factors, prefix, prev_k)
+    cats, facs = _tables(categories, replication_factors, prefix, k)
+    res = ctx.agree_table(k, prev_k, labels, prev_labels, sizes)  # [new][previous]
+    counts, nbytes = res if sizes is not None else (res, None)
+    return transition_from_table(counts.T, None if nbytes is None else nbytes.T, prev_cats,
+                                 prev_facs, cats, facs)
+
+
+NEW_FILES = "(new)"  # the previous category of the paths a previous plan does not hold
+
+
+def _previous_plan(path, paths, current_factor, prefix="C"):
+    """(labels, categories, factors, k) of the plan file `path` (one this module
+    wrote) for the files `paths`, joined on the path.  The previous clusters are
+    numbered 0.. in the order of their numbers in the file; the paths the file
+    does not hold form one more cluster of category ``NEW_FILES`` and factor
+    current_factor (SystemExit without it)."""
+    import pandas as pd
+
+    prev = pd.read_csv(path, usecols=HEADER, dtype={"path": str, "category": str},
+                       keep_default_na=False, na_filter=False)
+    per = prev.groupby("cluster")[["category", "replication"]].nunique()
+    if len(per) and int(per.to_numpy().max()) > 1:
+        raise SystemExit(f"Error: {path}: a cluster with more than one category or factor")
+    first = prev.drop_duplicates("cluster").sort_values("cluster")
+    dense = {int(c): j for j, c in enumerate(first["cluster"])}
+    cats = {f"{prefix}{j}": c for j, c in enumerate(first["category"])}
+    factors = {}
+    for c, f in zip(first["category"], first["replication"]):
+        if factors.setdefault(c, int(f)) != int(f):
+            raise SystemExit(f"Error: {path}: category {c!r} has more than one factor")
+    k = len(dense)
+    labels = paths.map(prev.drop_duplicates("path").set_index("path")["cluster"])
+    missing = labels.isna()
+    if missing.any():
+        if current_factor is None:
+            raise SystemExit(f"Error: {int(missing.sum())} paths are not in the previous plan "
+                             "(pass --current_factor for new files)")
+        if factors.setdefault(NEW_FILES, int(current_factor)) != int(current_factor):
+            raise SystemExit(f"Error: {path}: category {NEW_FILES!r} has another factor")
+        cats[f"{prefix}{k}"] = NEW_FILES
+        k += 1
+    lab = np.array([k - 1 if m else dense[int(c)] for c, m in zip(labels.fillna(0), missing)],
+                   dtype=np.int64)
+    return lab, cats, factors, k
+
+
 def _resolve(input_path):
     """src/main.py:154-168: a directory holds part-00000*.csv; the first match."""
     pattern = os.path.join(input_path, "part-00000*.csv") if os.path.isdir(input_path) \
@@ -344,6 +459,9 @@ def main(argv=None, context: Context | None = None):
     ap.add_argument("--out", default="plan.csv")
     ap.add_argument("--manifest", default=None, help="CSV with path and size_bytes columns")
     ap.add_argument("--current_factor", type=int, default=None)
+    ap.add_argument("--previous_plan", default=None,
+                    help="a plan CSV this program wrote earlier: the moves from it to the new "
+                         "plan are printed as one more JSON line")
     args = ap.parse_args(argv)
     src = _resolve(args.input_path)
     with open(args.tables) as fh:
@@ -360,19 +478,27 @@ def main(argv=None, context: Context | None = None):
     categories = clf.classify_labels(args.k, CLUSTERING_FEATURES, context=ctx)
     rows = write_plan_csv(src, args.out, categories, t["REPLICATION_FACTORS"], context=ctx)
     print(f"Wrote the plan of {rows} files to {args.out}")
-    if args.manifest:
+    sizes = None
+    if args.manifest or args.previous_plan:
         import pandas as pd
 
         paths = pd.read_csv(src, usecols=["path"], dtype=str, keep_default_na=False,
                             na_filter=False)["path"]
+    if args.manifest:
         man = pd.read_csv(args.manifest, usecols=["path", "size_bytes"],
                           dtype={"path": str}, keep_default_na=False, na_filter=False)
         sizes = paths.map(man.drop_duplicates("path").set_index("path")["size_bytes"])
         if sizes.isna().any():
             raise SystemExit(f"Error: {int(sizes.isna().sum())} paths are not in the manifest")
-        print(json.dumps(summarize(categories, t["REPLICATION_FACTORS"], args.k,
-                                   sizes=sizes.to_numpy(dtype=np.int64),
+        sizes = sizes.to_numpy(dtype=np.int64)
+        print(json.dumps(summarize(categories, t["REPLICATION_FACTORS"], args.k, sizes=sizes,
                                    current_factor=args.current_factor, context=ctx)))
+    if args.previous_plan:
+        prev_labels, prev_cats, prev_factors, prev_k = _previous_plan(
+            args.previous_plan, paths, args.current_factor)
+        print(json.dumps(transition(prev_cats, prev_factors, prev_k, categories,
+                                    t["REPLICATION_FACTORS"], args.k, prev_labels=prev_labels,
+                                    sizes=sizes, context=ctx)))
 
 
 if __name__ == "__main__":

@@ -699,6 +699,47 @@ int cdr_plan_timing(cdr_ctx* ctx, double* out);
 int cdr_plan_size_sums(cdr_ctx* ctx, const int64_t* labels, int64_t n, int32_t k,
                        const int64_t* sizes, uint64_t* out /* [k][2] */);
 
+/* ---- two clusterings of the same rows compared (extension: src/main.py:92 -- */
+/* ---- forms the cluster column and drops it, so no two runs can be compared) */
+/* The contingency table of two labelings a and b of the same n rows:
+ * counts[a][b] = the number of rows i with labels_a[i] == a and labels_b[i] == b,
+ * exact integers whatever the order of the adds.
+ *
+ * cdr_agree_keep: copies the labels of the last assignment device to device
+ *   into a buffer the context keeps, with their row count and their k.  The
+ *   kept labels survive later Lloyd steps and cdr_points_load_f64; only
+ *   another keep replaces them.  CDR_ERR_STATE without labels on the device.
+ * cdr_agree_table: labels_a: n host values in [0, ka), or NULL for the labels
+ *   of the last assignment resident in the context (n must be the context's
+ *   row count and ka >= their k).  labels_b: n host values in [0, kb), or NULL
+ *   for the kept labels (n must be the kept row count and kb >= the kept k).
+ *   1 <= ka, kb <= 1024, else CDR_ERR_UNSUPPORTED.  sizes: n host values >= 0,
+ *   and then for every cell size_sums[a][b][0] = the sum of the sizes' low 32
+ *   bits, size_sums[a][b][1] = the sum of their high 31 bits over the cell's
+ *   rows (neither can overflow; total = [0] + [1] * 2^32); sizes == NULL: the
+ *   counts alone, nothing is uploaded for sizes and size_sums must be NULL.
+ *   n == 0 gives zero tables.  Tables of at most cdr_agree_info's cap are
+ *   summed per workgroup in LDS, larger ones (up to 2^20 cells) with global
+ *   integer atomics; the results are the same.
+ *   CDR_ERR_ARG for a label out of range on either side, a negative size, n
+ *   other than a NULL side's row count, ka or kb below a NULL side's k, n
+ *   outside [0, 2^31), or size_sums without sizes (and the reverse);
+ *   CDR_ERR_STATE for a NULL side with nothing resident or kept.  After any
+ *   error the context stays usable, and a call changes nothing else in it: the
+ *   points, the resident and the kept labels, the grouped medians and the
+ *   plan's record index are not touched.
+ * cdr_agree_info: out[4] = {form of the last cdr_agree_table (0: LDS, 1:
+ *   global, -1: none yet), the LDS form's cell cap without sizes, its cap with
+ *   sizes, workgroups of the last launch (0: none, n == 0)}.
+ * cdr_agree_timing: out[3] = {uploads and zeroing, kernel, copy back} ms of the
+ *   last cdr_agree_table, from HIP events.                                   */
+int cdr_agree_keep(cdr_ctx* ctx);
+int cdr_agree_table(cdr_ctx* ctx, const int64_t* labels_a, int32_t ka, const int64_t* labels_b,
+                    int32_t kb, int64_t n, const int64_t* sizes,
+                    uint64_t* counts /* [ka][kb] */, uint64_t* size_sums /* [ka][kb][2] or NULL */);
+int cdr_agree_info(cdr_ctx* ctx, int64_t* out);
+int cdr_agree_timing(cdr_ctx* ctx, double* out);
+
 /* ---- cluster quality (extension: no reference counterpart) ------------- */
 /* Validity indices of a clustering of the resident points, for choosing the
  * k the reference fixes (src/main.py --k).  The distance is the reference's
