@@ -166,6 +166,9 @@ SIGNATURES = {
     "cdr_agree_table": ([_P, _P, _I32, _P, _I32, _I64, _P, _P, _P], None),
     "cdr_agree_info": ([_P, _P], None),
     "cdr_agree_timing": ([_P, _P], None),
+    "cdr_place_replicas": ([_P, _I32, _P, _I64, _I32, _P, _I32, _P, _P, _P, _P, _P, _P], None),
+    "cdr_place_info": ([_P, _P], None),
+    "cdr_place_timing": ([_P, _P], None),
     "cdr_host_seq_sum": ([_P, _I64, _F64], ctypes.c_double),
 }
 
@@ -974,6 +977,7 @@ class Context:
         _check(self._lib.cdr_ingest_manifest(self._h, len(po) - 1, _ptr(pb), _ptr(po),
                                              _ptr(primary), len(no) - 1, _ptr(nb), _ptr(no)))
         self._ing_nf = len(po) - 1
+        self._ing_nodes = len(no) - 1
 
     def ingest_log(self, data) -> np.ndarray:
         """Parse the log bytes on the device into the resident events.  Returns
@@ -1284,6 +1288,60 @@ class Context:
         """{uploads, kernel, copy back} ms of the last agree_table."""
         out = np.zeros(3, dtype=np.float64)
         _check(self._lib.cdr_agree_timing(self._h, _ptr(out)))
+        return out
+
+    # -- replica placement on the device (csrc/place.hip) --------------------
+    def place_replicas(self, n_nodes: int, k: int, factors, R: int, labels=None, sizes=None,
+                       per_file: bool = True, counts: bool = False) -> dict:
+        """Where the replicas of every file of the resident events go
+        (cdr_place_replicas).  ``factors``: int32 (k,) in [0, R]; ``labels``
+        None: the resident labels; ``sizes``: int64 >= 0, one per file.
+        Returns ``nodes`` int32 (n_files, R) (-1 past the file's factor),
+        ``per_file`` int64 (n_files, 3) = total, local_before, local_after (None
+        unless asked), ``counts`` int64 (n_files, n_nodes) (None unless asked),
+        ``cluster_sums`` int64 (k, 3), ``node_replicas`` int64 (n_nodes,) and
+        ``node_bytes``, a list of exact Python ints."""
+        nf = self._ev[1] if getattr(self, "_ev", None) else 0
+        n_nodes, k, R = int(n_nodes), int(k), int(R)
+        factors = np.ascontiguousarray(factors, dtype=np.int32).ravel()
+        if factors.size != max(k, 0):
+            raise ValueError(f"{factors.size} factors for k = {k}")
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        if sizes is not None:
+            sizes = np.ascontiguousarray(sizes, dtype=np.int64).ravel()
+            if sizes.size != nf:
+                raise ValueError(f"{sizes.size} sizes for {nf} files")
+        # (a k, R or n_nodes out of range: the library's error, on arrays that hold any)
+        nn1, k1, r1 = min(max(n_nodes, 1), 64), min(max(k, 1), 1024), min(max(R, 1), 8)
+        nodes = np.full((nf, r1), -1, dtype=np.int32)
+        pf = np.zeros((nf, 3), dtype=np.int64) if per_file else None
+        cnt = np.zeros((nf, nn1), dtype=np.int64) if counts else None
+        csum = np.zeros((k1, 3), dtype=np.uint64)
+        nsum = np.zeros((nn1, 3), dtype=np.uint64)
+        if factors.size == 0:
+            factors = np.zeros(1, dtype=np.int32)
+        _check(self._lib.cdr_place_replicas(
+            self._h, n_nodes, None if lab is None else _ptr(lab), 0 if lab is None else lab.size,
+            k, _ptr(factors), R, None if sizes is None else _ptr(sizes), _ptr(nodes),
+            None if pf is None else _ptr(pf), None if cnt is None else _ptr(cnt), _ptr(csum),
+            _ptr(nsum)))
+        return {"nodes": nodes, "per_file": pf, "counts": cnt,
+                "cluster_sums": csum.astype(np.int64),
+                "node_replicas": nsum[:, 0].astype(np.int64),
+                "node_bytes": [int(nsum[j, 1]) + (int(nsum[j, 2]) << 32) for j in range(nn1)]}
+
+    def place_info(self) -> dict:
+        """cdr_place_info: what the last place_replicas did."""
+        out = np.zeros(6, dtype=np.int64)
+        _check(self._lib.cdr_place_info(self._h, _ptr(out)))
+        return {"form": int(out[0]), "L": int(out[1]), "buckets": int(out[2]),
+                "workgroups": int(out[3]), "reused": int(out[4]), "payload_bytes": int(out[5])}
+
+    def place_timing(self) -> np.ndarray:
+        """{partition (0 when reused), uploads and zeroing, kernels, copies back}
+        ms of the last place_replicas."""
+        out = np.zeros(4, dtype=np.float64)
+        _check(self._lib.cdr_place_timing(self._h, _ptr(out)))
         return out
 
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/cdr.h"
+#include "groupby_pay.h"
 
 namespace cdr {
 
@@ -102,7 +103,7 @@ constexpr int kPointGroup = 64;   // points per wave iteration in the screen
 // (CDR_BOUNDS, CDR_NO_DELTA, CDR_S32B_SPLIT, CDR_S32BS_SPLIT, CDR_EXACT_ASSIGN,
 // CDR_F64_SERIAL, CDR_F64S_FORCE_CHAIN, CDR_GROUPBY_SORT, CDR_GB_BLOCK,
 // CDR_GB_BALLOT, CDR_GB_PASS3, CDR_S32BS_CUS, CDR_S32BS_DYN_MIN, CDR_QUALITY_BUDGET,
-// CDR_S32BS_WATCH, CDR_S32BS_WATCH_MIN, CDR_S32BS_WATCH_BETA, CDR_S32BS_WATCH_CAP, CDR_GMED_GRID) are read with
+// CDR_S32BS_WATCH, CDR_S32BS_WATCH_MIN, CDR_S32BS_WATCH_BETA, CDR_S32BS_WATCH_CAP, CDR_GMED_GRID, CDR_PLACE_GLOBAL) are read with
 // getenv in both builds.
 inline const char* exp_env(const char* name) {
 #ifdef CDR_EXPERIMENTS
@@ -412,6 +413,18 @@ struct Ctx {
   int gb_last_hand = 0, gb_last_L = 0, gb_last_passes = 0, gb_last_pbytes = 0, gb_last_big = 0,
       gb_last_dense = 0;
   int64_t gb_last_grid = 0;
+  // the resident partition (groupby_pay.h): set by groupby_resident, dropped
+  // by every writer of the resident events
+  GbPartition gb_part_rec;
+  bool ev_foreign = false;  // the event buffers hold cdr_features_aggregate's host events
+  // place.hip: explicit labels as int32 and their pinned staging, the factors,
+  // the sizes, the nodes / per-file / count rows, the global form's table, the
+  // sums {cluster, node, flag} and their pinned copy; what the last call did
+  // (cdr_place_info) and its {partition, uploads, kernels, copies} ms
+  DevBuf pl_lab, pl_fac, pl_sz, pl_nodes, pl_pf, pl_cnt, pl_tab, pl_sum;
+  HostBuf pl_stage, pl_host;
+  int64_t pl_info[6] = {-1, 0, 0, 0, 0, 0};
+  double pl_ms[4] = {0.0, 0.0, 0.0, 0.0};
 
   // ---- access-log ingest (ingest.hip) ----
   DevBuf ing_log;              // log bytes, zero-padded to a whole tile
@@ -498,6 +511,16 @@ inline void step_done(Ctx& c, int k, int64_t fallback) {
   c.have_labels = true;
   c.med_k = 0;  // new labels: the grouped rows (medians.hip) are stale
   c.last_fallback = fallback;
+}
+
+// Whatever rewrites the resident events (c.ev_file / ev_client / ev_ts) or the
+// gb_ buffers drops the resident partition: place.hip then builds it again.
+// The loaders call it; features_aggregate, whose host events overwrite the
+// buffers without becoming the resident (ev_n, ev_nf) ones, sets ev_foreign
+// instead, and place.hip refuses to run until a loader has cleared it.
+inline void drop_partition(Ctx& c) {
+  c.gb_part_rec.valid = false;
+  c.ev_foreign = false;
 }
 
 void seed_reset(Ctx& c);

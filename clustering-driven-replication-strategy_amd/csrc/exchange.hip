@@ -206,6 +206,7 @@ int cdr_features_exchange_unpack(cdr_ctx* h, const void* recv, int64_t n, int64_
   if (n < 0 || n >= (1ll << 31)) CDR_FAIL(CDR_ERR_ARG, "exchange: 0 <= n < 2^31");
   HIP_CHECK(hipSetDevice(c.device));
   const size_t n1 = n > 0 ? (size_t)n : 1;
+  drop_partition(c);  // the events are rewritten
   c.x_buf.ensure(sizeof(XRec) * n1);
   if (n > 0)
     HIP_CHECK(hipMemcpyAsync(c.x_buf.p, recv, sizeof(XRec) * n, hipMemcpyDefault, c.stream));
@@ -253,6 +254,7 @@ int cdr_features_load_events(cdr_ctx* h, int64_t n, const int32_t* file, const u
   Ctx& c = h->c;
   HIP_CHECK(hipSetDevice(c.device));
   const size_t n1 = n > 0 ? (size_t)n : 1, f1 = n_files > 0 ? (size_t)n_files : 1;
+  drop_partition(c);  // the events are rewritten
   c.ev_file.ensure(4 * n1);
   c.ev_op.ensure(n1);
   c.ev_client.ensure(4 * n1);

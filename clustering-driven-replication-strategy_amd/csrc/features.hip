@@ -353,6 +353,8 @@ void features_aggregate(Ctx& c, int64_t ne, const int32_t* file_idx, const uint8
   *max_ts = LLONG_MIN;
   if (n_files == 0 && ne == 0) return;
   ensure_events(c, ne, n_files);
+  c.gb_part_rec.valid = false;
+  c.ev_foreign = true;  // the buffers no longer hold the resident (ev_n, ev_nf) events
   if (ne > 0) {
     HIP_CHECK(hipMemcpyAsync(c.ev_file.p, file_idx, 4 * ne, hipMemcpyHostToDevice, c.stream));
     HIP_CHECK(hipMemcpyAsync(c.ev_op.p, op, ne, hipMemcpyHostToDevice, c.stream));
@@ -367,6 +369,7 @@ void features_aggregate(Ctx& c, int64_t ne, const int32_t* file_idx, const uint8
   for (int64_t i = 0; i < ne; ++i) cmax = std::max(cmax, (int)client[i]);
   c.ev_cmax = cmax;
   features_aggregate_resident(c, ne, n_files, out, max_ts);
+  c.gb_part_rec.valid = false;  // the partition just built is of these events, not the resident ones
 }
 
 // The group-by over the events resident in c.ev_* (uploaded or generated).
@@ -548,6 +551,7 @@ void features_generate(Ctx& c, int64_t ne, int64_t n_files, unsigned long long s
   if (n_files >= (1ll << 31)) CDR_FAIL(CDR_ERR_UNSUPPORTED, "n_files >= 2^31");
   if (ne > 0 && span_us > (long long)(LLONG_MAX / ne)) CDR_FAIL(CDR_ERR_ARG, "span too large");
   ensure_events(c, ne, n_files);
+  drop_partition(c);
   hipLaunchKernelGGL(gen_events, dim3(8192), dim3(256), 0, c.stream, ne, n_files, seed, t0_us,
                      span_us, c.ev_file.as<int32_t>(), c.ev_op.as<uint8_t>(),
                      c.ev_client.as<int32_t>(), c.ev_ts.as<long long>(),

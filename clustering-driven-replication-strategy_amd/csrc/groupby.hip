@@ -49,7 +49,6 @@ constexpr int kGbBThreads = 256;                // bucket workgroups
 constexpr int kGbSlots = 4096;                  // LDS hash slots per bucket
 constexpr int kGbLdsCap = 3072;                 // events per bucket in LDS (load <= 3/4)
 constexpr int kGbReg = kGbLdsCap / kGbBThreads; // payloads per bucket thread
-constexpr int kGbMaxL = 10;                     // files per bucket <= 1024
 constexpr long long kTsNullG = LLONG_MIN;
 constexpr unsigned long long kEmpty = ~0ull;
 
@@ -59,17 +58,7 @@ __device__ __forceinline__ long long sec_of_g(long long ts_us) {
   return (long long)floor((double)ts_us / 1000000.0);
 }
 
-// Payload layout (host-computed, passed by value).
-struct GbPay {
-  int fshift;   // bit position of the file-low field
-  int sshift;   // bit position of the second code (= 2 + cbits)
-  int cbits;    // client code bits (code 0 = not a node id, else client + 1)
-  int sbits;    // second code bits (all ones = null)
-  int L;        // file-local bits (files per bucket = 2^L)
-  long long sec_min;
-  unsigned long long low_mask;  // file-low field mask (fbits - B1 bits)
-};
-
+// (GbPay, the payload layout, and kGbMaxL: groupby_pay.h)
 template <typename T>
 __device__ __forceinline__ T gb_make(const GbPay& p, unsigned flow, long long ts, uint8_t op,
                                      int client) {
@@ -1486,6 +1475,15 @@ void gb_run(Ctx& c, int64_t ne, int64_t nf, int fbits, int L, int B1, int B2, in
     prof_mark(c, 2);
   }
   c.gb_last_big = nbig;
+  // the partition stays resident for place.hip
+  c.gb_part_rec.valid = true;
+  c.gb_part_rec.ne = ne;
+  c.gb_part_rec.nf = nf;
+  c.gb_part_rec.nb = nb;
+  c.gb_part_rec.pay = pb;
+  c.gb_part_rec.bbase = bbase;
+  c.gb_part_rec.pbytes = (int)sizeof(T);
+  c.gb_part_rec.p = p;
   if (out)
     HIP_CHECK(hipMemcpyAsync(out, c.ev_out.p, 8 * 6 * nf, hipMemcpyDeviceToHost, c.stream));
   HIP_CHECK(hipStreamSynchronize(c.stream));
@@ -1522,6 +1520,7 @@ void events_ts_range(Ctx& c, int64_t ne) {
 // else the hash with about 1024 events per bucket.
 bool groupby_resident(Ctx& c, int64_t ne, int64_t nf, int64_t* out, int64_t* max_ts) {
   c.gb_last_hand = 0;
+  c.gb_part_rec.valid = false;  // the gb_ buffers are rewritten (or the sort-based path runs)
   if (nf < 1 || ne < 0 || ne >= (1ll << 31) || nf >= (1ll << 31)) return false;
   if (getenv("CDR_GROUPBY_SORT")) return false;  // the sort-based path, for comparisons
   const int cmax = c.ev_cmax;

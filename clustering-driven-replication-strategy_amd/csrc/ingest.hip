@@ -636,6 +636,7 @@ void ingest_manifest(Ctx& c, int64_t n_files, const char* pbytes, const int64_t*
   c.ing_nfiles = n_files;
   c.ev_n = 0;
   c.ev_tsr_valid = false;
+  drop_partition(c);
   c.ev_nf = 0;
 }
 
@@ -676,6 +677,7 @@ void ingest_parse(Ctx& c, int64_t* status) {
     tail = r6[5] != 0;
   }
   const int64_t ne1 = nrec > 0 ? nrec : 1;
+  drop_partition(c);  // the events are rewritten
   c.ing_ends.ensure(8 * ne1);
   c.ev_file.ensure(4 * ne1);
   c.ev_op.ensure(ne1);

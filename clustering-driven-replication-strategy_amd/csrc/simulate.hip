@@ -231,6 +231,7 @@ int64_t features_simulate(Ctx& c, int64_t nf, int64_t file_begin, double duratio
   if (!(duration_s > 0) || duration_s > 1e7) CDR_FAIL(CDR_ERR_ARG, "simulate: duration");
   if (n_clients < 1) CDR_FAIL(CDR_ERR_ARG, "simulate: n_clients >= 1");
   // per-file counts and primaries
+  drop_partition(c);  // the events and the primaries are rewritten
   DevBuf& cnt = c.sim_cnt;
   cnt.ensure(sizeof(long long) * (nf + 1));
   c.ev_primary.ensure(4 * (size_t)nf);

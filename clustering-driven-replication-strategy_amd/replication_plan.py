@@ -28,6 +28,7 @@ CLI (the join of ``size_bytes`` on ``path`` for ``--manifest`` is host work, pan
     python replication_plan.py --input_path F --k K --tables T.json --out plan.csv
                                [--manifest M.csv] [--current_factor R]
                                [--previous_plan PREV.csv]
+                               [--access_log LOG --placement PLACEMENT.csv]
 
 From the second plan on each file already carries the previous plan's factor,
 so what a new plan costs is summed per file against that: ``transition`` (the
@@ -35,6 +36,12 @@ moves between the categories of two plans) from the contingency table of the
 two clusterings (csrc/agree.hip, cluster_agreement.py), weighted by the sizes.
 ``--previous_plan`` (a file this module wrote; joined on ``path`` by pandas)
 prints it as one more JSON line after ``summarize``'s.
+
+``--access_log`` with ``--manifest`` and ``--placement`` also writes where the
+replicas go (``path,replication,nodes``; replica_placement.py, csrc/place.hip)
+and prints one more JSON line: the share of node-local accesses before and
+after, overall and per category, and the replicas and bytes per node.  Without
+them every output is what it was.
 """
 from __future__ import annotations
 
@@ -462,7 +469,15 @@ def main(argv=None, context: Context | None = None):
     ap.add_argument("--previous_plan", default=None,
                     help="a plan CSV this program wrote earlier: the moves from it to the new "
                          "plan are printed as one more JSON line")
+    ap.add_argument("--access_log", default=None,
+                    help="the access log the features were built from (with --manifest and "
+                         "--placement): the nodes of each file's replicas")
+    ap.add_argument("--placement", default=None,
+                    help="where to write path,replication,nodes (replica_placement.py)")
     args = ap.parse_args(argv)
+    if (args.access_log is None) != (args.placement is None) or (
+            args.placement is not None and args.manifest is None):
+        raise SystemExit("Error: --access_log, --placement and --manifest go together")
     src = _resolve(args.input_path)
     with open(args.tables) as fh:
         t = json.load(fh)
@@ -499,6 +514,14 @@ def main(argv=None, context: Context | None = None):
         print(json.dumps(transition(prev_cats, prev_factors, prev_k, categories,
                                     t["REPLICATION_FACTORS"], args.k, prev_labels=prev_labels,
                                     sizes=sizes, context=ctx)))
+    if args.placement:
+        import replica_placement as rp
+
+        res = rp.place_from_log(args.manifest, args.access_log, src, categories,
+                                t["REPLICATION_FACTORS"], args.k, context=ctx)
+        rp.write_placement_csv(args.placement, res["paths"], res["factors"], res["nodes"],
+                               res["node_names"])
+        print(json.dumps(dict(rp.summary_json(res["summary"]), node_names=res["node_names"])))
 
 
 if __name__ == "__main__":

@@ -740,6 +740,61 @@ int cdr_agree_table(cdr_ctx* ctx, const int64_t* labels_a, int32_t ka, const int
 int cdr_agree_info(cdr_ctx* ctx, int64_t* out);
 int cdr_agree_timing(cdr_ctx* ctx, double* out);
 
+/* ---- replica placement (extension: no reference counterpart; the reference -- */
+/* ---- stops at a replication factor per category, src/main.py:92) ---------- */
+/* Where each file's replicas go, from the client node of every resident event
+ * (cdr_features_load_events, _generate, _simulate, cdr_ingest_log, the
+ * exchange).  For file f and node j < n_nodes, cnt[f][j] = its events with
+ * client == j; total[f] = all its events (a client that is negative or >=
+ * n_nodes counts in the total only; events with a file outside [0, n_files)
+ * are ignored).  The node order of f: its primary first when 0 <= primary <
+ * n_nodes, then the other nodes by descending cnt, ties to the lower id.  The
+ * first min(factor, n_nodes) of that order are its nodes, factor =
+ * factors[labels[f]].  All results are exact integers in any order of the adds.
+ *
+ * cdr_place_replicas (extension, no reference counterpart): n_nodes in
+ *   [1, 64] and k in [1, 1024], else CDR_ERR_UNSUPPORTED; R in [1, 8].
+ *   labels: n_labels host values in [0, k) (n_labels must be the events'
+ *   n_files), or NULL for the labels of the last assignment resident in the
+ *   context (their row count must be n_files, k >= their k).  factors: k
+ *   values in [0, R].  sizes: n_files host values >= 0, or NULL.
+ *   nodes_out [n_files][R]: the chosen nodes, then -1.  per_file_out
+ *   [n_files][3] (may be NULL) = {total, local_before = cnt[f][primary] (0
+ *   without a valid primary), local_after = the sum of cnt over the chosen
+ *   nodes}.  counts_out [n_files][n_nodes] (may be NULL) = cnt.  cluster_sums
+ *   [k][3] = the per_file columns summed over each cluster's files.  node_sums
+ *   [n_nodes][3] = {replicas placed on the node, the sum of their sizes' low
+ *   32 bits, of their high 31 bits} (bytes = [1] + [2] * 2^32; zeros without
+ *   sizes).
+ *   The bucket form reads the partition the group-by left resident
+ *   (cdr_features_aggregate_resident), or builds it first when the events
+ *   were rewritten since; one wave counts a bucket of 2^L files in LDS.  When
+ *   the group-by does not take the shape (or CDR_GROUPBY_SORT=1 keeps it off
+ *   the partition), when (4 << L) * n_nodes exceeds
+ *   12288 bytes, or with CDR_PLACE_GLOBAL=1 in the environment, the global
+ *   form counts into a [n_files][n_nodes + 1] table with integer atomics
+ *   (n_files * n_nodes <= 2^30, else CDR_ERR_UNSUPPORTED).  Same results.
+ *   CDR_ERR_ARG: a label or factor out of range, a negative size, n_labels
+ *   other than n_files, R out of range; CDR_ERR_STATE: no resident events, or
+ *   NULL labels with none on the device.  After any error the context stays
+ *   usable.  cdr_features_aggregate (host events in one call) overwrites the
+ *   event buffers without making its events the resident ones: a placement
+ *   after it is CDR_ERR_STATE until a loader (cdr_features_load_events, ...)
+ *   makes events resident again.  A successful call leaves the points, the resident and kept
+ *   labels, the grouped medians, the plan's record index and the events as
+ *   they were.
+ * cdr_place_info (extension): out[6] = {form of the last call (0 bucket, 1
+ *   global, -1 none), L, buckets, workgroups launched, 1 if the resident
+ *   partition was reused (0: built by the call), payload bytes}.
+ * cdr_place_timing (extension): out[4] = {partition (0 when reused), uploads
+ *   and zeroing, kernels, copies back} ms of the last call, from HIP events. */
+int cdr_place_replicas(cdr_ctx* ctx, int32_t n_nodes, const int64_t* labels, int64_t n_labels,
+                       int32_t k, const int32_t* factors, int32_t R, const int64_t* sizes,
+                       int32_t* nodes_out, int64_t* per_file_out, int64_t* counts_out,
+                       uint64_t* cluster_sums /* [k][3] */, uint64_t* node_sums /* [n_nodes][3] */);
+int cdr_place_info(cdr_ctx* ctx, int64_t* out);
+int cdr_place_timing(cdr_ctx* ctx, double* out);
+
 /* ---- cluster quality (extension: no reference counterpart) ------------- */
 /* Validity indices of a clustering of the resident points, for choosing the
  * k the reference fixes (src/main.py --k).  The distance is the reference's
