@@ -149,15 +149,17 @@ struct Ctx {
   // the points row-major (float [n_pad][d4]): the gathers of the fused fixup,
   // of screen32bs, of the large-k path and of the seeding
   DevBuf xa32;
-  // large-k screen copy (screen_big_sp): fp16 of the pre-centred points as the
-  // MFMA B fragments are loaded, [n_pad/64][2 tiles][DQ chunks][64 lanes] x 16 B
+  // large-k screen copy (big_ensure_xb, screen_big_l1.hip; read by L1 and both
+  // L2 forms): fp16 of the pre-centred points as the MFMA B fragments are
+  // loaded, [n_pad/64][2 tiles][DQ chunks][64 lanes] x 16 B
   DevBuf xb16;
   bool xb_valid = false;
   bool xa_valid = false;  // xa32 built (ensure_rowmajor)
-  // large-k running sums (screen_big DELTA steps): int64 (k, d+1) of the
-  // current labels, valid while only large-k steps of k = big_k wrote them
+  // large-k running sums (big_launch_sums, screen_big_sums.hip): int64
+  // (k, d+1) of the current labels, valid while only large-k steps of
+  // k = big_k wrote them; a valid set makes the next such step a DELTA step
   DevBuf big_sums;
-  DevBuf big_chunks;  // L2 chunk numbering of L1's regions (big_chunk_prefix)
+  DevBuf big_chunks;  // cand_big_lds: chunk numbering of L1's regions (big_chunk_prefix)
   bool big_valid = false;
   int big_k = 0;
   // the last large-k launch (cdr_lloyd_big_layout): DQ, KB, FG, JB, L1 threads,
@@ -478,7 +480,7 @@ bool big_step(Ctx& c, const double* C, int k, long long* dout, bool prof);
 // test hooks (lloyd.hip's cdr_debug_* and layout entry points)
 void debug_plan32(Ctx& c, int which, const double* C, int k, float* out);  // screen32.hip
 void big_layout_read(Ctx& c, int64_t out[15]);                        // screen_big.hip
-int64_t debug_big_plan(Ctx& c, int k, void* out, int64_t bytes);     // screen_big.hip
+int64_t debug_big_plan(Ctx& c, int k, void* out, int64_t bytes);     // screen_big_plan.hip
 // lloyd_exact.hip: enqueue on the context stream.  Exact labels of every point
 // from c.cent64 (x32 or x64 by the mode); (k, d+1) int64 sums of the labels
 // into the zeroed dout; sum of c.partials' nwg tables (row stride KS) into

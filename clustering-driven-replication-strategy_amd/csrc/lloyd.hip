@@ -200,7 +200,7 @@ int cdr_lloyd_big_layout(cdr_ctx* h, int64_t out[15]) {
   CDR_CATCH
 }
 
-// Test hook: the large-k plan buffer of the last large-k step (screen_big.hip).
+// Test hook: the large-k plan buffer of the last large-k step (screen_big_plan.hip).
 int cdr_debug_big_plan(cdr_ctx* h, int32_t k, void* out, int64_t bytes, int64_t* written) {
   CDR_TRY
   if (!h || !written) CDR_FAIL(CDR_ERR_ARG, "null argument");

@@ -257,7 +257,9 @@ static double points_sqdev(Ctx& c, const double* ref_host) {
 
 void plan32_launch(Ctx& c, int k, int QH, int MT);  // screen32.hip
 bool big_supported(const Ctx& c, int k);              // screen_big.hip
+// screen_big_plan.hip
 void big_plan_device(Ctx& c, int k, const double* dC, const double* dmu, const long long* gate);
+// screen_big.hip
 bool big_step_dev(Ctx& c, int k, long long* dout, bool prof, const long long* gate);
 
 // Large-k plan of the loop's current centroids (begin, resume, and after

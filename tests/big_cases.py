@@ -70,7 +70,7 @@ from oracle import synth
 
 GRID_BITS = 10
 UNIT = 2.0 ** -GRID_BITS
-KMAXCAND = 16                 # kMaxCand of csrc/screen_big.hip
+KMAXCAND = 16                 # kMaxCand of csrc/screen_big.h
 CLUSTER_M = (2, 15, 16, 17, 40)
 DELTA = (96, 80)              # grid units in two coordinates
 EDGES = (32, 1024, 2048, 4096)
@@ -83,8 +83,8 @@ SHAPES = {(64, 1100): 4000, (40, 1500): 5000, (20, 2200): 6000, (12, 4200): 8000
 
 
 def form(d: int, k: int) -> dict:
-    """The form the host code of csrc/screen_big.hip picks for (d, k), from the
-    formulas of its big_supported, big_launch and launch_big_levels."""
+    """The form the host code of csrc/screen_big*.hip picks for (d, k), from the
+    formulas of its big_supported, big_launch and the levels' launchers."""
     DQ, KB = -(-d // 16), -(-k // 32)
     lds1 = KB * 128 + KB * DQ * 1024
     fg = next((g for g in (16, 8, 4) if k * (g * 8 + 4) <= 150 * 1024), 0)

@@ -1,4 +1,4 @@
-// Microbenchmark of the config-5 L1 screen loop (csrc/screen_big.hip
+// Microbenchmark of the config-5 L1 screen loop (csrc/screen_big_l1.hip
 // screen_big_sp) on synthetic fragments, chip-wide, with ablations:
 //   mode 0 full, 1 MFMA + minimal VALU (one v_min per block), 2 VALU only
 //   (no MFMA: the C rows stand in for the products), 3 full but A fragments
