@@ -169,6 +169,9 @@ SIGNATURES = {
     "cdr_place_replicas": ([_P, _I32, _P, _I64, _I32, _P, _I32, _P, _P, _P, _P, _P, _P], None),
     "cdr_place_info": ([_P, _P], None),
     "cdr_place_timing": ([_P, _P], None),
+    "cdr_place_evaluate": ([_P, _I32, _P, _I32, _P, _I64, _I32, _P, _P, _P], None),
+    "cdr_place_evaluate_info": ([_P, _P], None),
+    "cdr_place_evaluate_timing": ([_P, _P], None),
     "cdr_host_seq_sum": ([_P, _I64, _F64], ctypes.c_double),
 }
 
@@ -1342,6 +1345,50 @@ class Context:
         ms of the last place_replicas."""
         out = np.zeros(4, dtype=np.float64)
         _check(self._lib.cdr_place_timing(self._h, _ptr(out)))
+        return out
+
+    # -- a given placement judged on the device (csrc/place_eval.hip) --------
+    def place_evaluate(self, n_nodes: int, nodes, k: int, labels=None,
+                       per_file: bool = False) -> dict:
+        """How local the placement ``nodes`` (int32 (n_files, R), entries in
+        [-1, n_nodes)) is under the resident events, and what it costs
+        (cdr_place_evaluate).  ``labels`` None: the resident labels.  Returns
+        int64 arrays: ``per_file`` (n_files, 2) = total, local (None unless
+        asked), ``cluster_sums`` (k, 6) = events, local, reads, reads_local,
+        writes, write_copies and ``node_sums`` (n_nodes, 5) = issued, local,
+        reads_served, writes_received, replicas."""
+        nf = self._ev[1] if getattr(self, "_ev", None) else 0
+        n_nodes, k = int(n_nodes), int(k)
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        if nodes.ndim != 2 or nodes.shape[0] != nf:
+            raise ValueError(f"nodes of shape {nodes.shape} for {nf} files")
+        R = int(nodes.shape[1])
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        # (a k, R or n_nodes out of range: the library's error, on arrays that hold any)
+        nn1, k1 = min(max(n_nodes, 1), 64), min(max(k, 1), 1024)
+        pf = np.zeros((nf, 2), dtype=np.int64) if per_file else None
+        csum = np.zeros((k1, 6), dtype=np.uint64)
+        nsum = np.zeros((nn1, 5), dtype=np.uint64)
+        if nodes.size == 0:
+            nodes = np.full((1, 1), -1, dtype=np.int32)
+        _check(self._lib.cdr_place_evaluate(
+            self._h, n_nodes, _ptr(nodes), R, None if lab is None else _ptr(lab),
+            0 if lab is None else lab.size, k, None if pf is None else _ptr(pf), _ptr(csum),
+            _ptr(nsum)))
+        return {"per_file": pf, "cluster_sums": csum.astype(np.int64),
+                "node_sums": nsum.astype(np.int64)}
+
+    def place_evaluate_info(self) -> dict:
+        """cdr_place_evaluate_info: what the last place_evaluate did."""
+        out = np.zeros(3, dtype=np.int64)
+        _check(self._lib.cdr_place_evaluate_info(self._h, _ptr(out)))
+        return {"form": int(out[0]), "workgroups": int(out[1]), "workgroup_events": int(out[2])}
+
+    def place_evaluate_timing(self) -> np.ndarray:
+        """{uploads and zeroing, file pass, event kernel, copies back} ms of
+        the last place_evaluate."""
+        out = np.zeros(4, dtype=np.float64)
+        _check(self._lib.cdr_place_evaluate_timing(self._h, _ptr(out)))
         return out
 
 

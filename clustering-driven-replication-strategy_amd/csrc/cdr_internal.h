@@ -427,6 +427,15 @@ struct Ctx {
   HostBuf pl_stage, pl_host;
   int64_t pl_info[6] = {-1, 0, 0, 0, 0, 0};
   double pl_ms[4] = {0.0, 0.0, 0.0, 0.0};
+  // place_eval.hip: the given nodes table, explicit labels as int32, the
+  // 16-byte file records, the uint32 per-file table, the sums {cluster, node,
+  // flag}; the pinned staging of nodes and labels and the pinned copy of the
+  // sums and the per-file table; what the last call did
+  // (cdr_place_evaluate_info) and its {uploads, file pass, events, copies} ms
+  DevBuf pe_nodes, pe_lab, pe_rec, pe_pf, pe_sum;
+  HostBuf pe_stage, pe_host;
+  int64_t pe_info[3] = {-1, 0, 0};
+  double pe_ms[4] = {0.0, 0.0, 0.0, 0.0};
 
   // ---- access-log ingest (ingest.hip) ----
   DevBuf ing_log;              // log bytes, zero-padded to a whole tile

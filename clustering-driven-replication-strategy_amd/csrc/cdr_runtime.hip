@@ -474,10 +474,12 @@ int cdr_destroy(cdr_ctx* h) {
                     &c.plan_part, &c.plan_def, &c.plan_out, &c.plan_sz, &c.plan_sum,
                     &c.agree_kept, &c.agree_a, &c.agree_b, &c.agree_sz, &c.agree_tab,
                     &c.pl_lab, &c.pl_fac, &c.pl_sz, &c.pl_nodes, &c.pl_pf, &c.pl_cnt, &c.pl_tab,
-                    &c.pl_sum};
+                    &c.pl_sum, &c.pe_nodes, &c.pe_lab, &c.pe_rec, &c.pe_pf, &c.pe_sum};
   for (DevBuf* b : bufs) b->release();
   c.pl_stage.release();
   c.pl_host.release();
+  c.pe_stage.release();
+  c.pe_host.release();
   c.agree_stage.release();
   c.agree_host.release();
   c.h_small.release();

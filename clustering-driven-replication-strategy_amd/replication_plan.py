@@ -29,6 +29,7 @@ CLI (the join of ``size_bytes`` on ``path`` for ``--manifest`` is host work, pan
                                [--manifest M.csv] [--current_factor R]
                                [--previous_plan PREV.csv]
                                [--access_log LOG --placement PLACEMENT.csv]
+                               [--access_log LOG --evaluate_placement EARLIER.csv]
 
 From the second plan on each file already carries the previous plan's factor,
 so what a new plan costs is summed per file against that: ``transition`` (the
@@ -42,6 +43,13 @@ replicas go (``path,replication,nodes``; replica_placement.py, csrc/place.hip)
 and prints one more JSON line: the share of node-local accesses before and
 after, overall and per category, and the replicas and bytes per node.  Without
 them every output is what it was.
+
+``--access_log`` with ``--manifest`` and ``--evaluate_placement`` judges a
+placement CSV written earlier (yesterday's, or a cluster's real block
+locations) on this log (replica_placement.evaluate, csrc/place_eval.hip) and
+prints one more JSON line: locality, read locality and write amplification
+overall and per category, and per node the events issued, the reads served,
+the write copies received and the replicas.
 """
 from __future__ import annotations
 
@@ -474,10 +482,15 @@ def main(argv=None, context: Context | None = None):
                          "--placement): the nodes of each file's replicas")
     ap.add_argument("--placement", default=None,
                     help="where to write path,replication,nodes (replica_placement.py)")
+    ap.add_argument("--evaluate_placement", default=None,
+                    help="a placement CSV written earlier (with --manifest and --access_log): "
+                         "how local it is under this log and what it costs, as one more JSON "
+                         "line")
     args = ap.parse_args(argv)
-    if (args.access_log is None) != (args.placement is None) or (
-            args.placement is not None and args.manifest is None):
-        raise SystemExit("Error: --access_log, --placement and --manifest go together")
+    uses_log = args.placement is not None or args.evaluate_placement is not None
+    if (args.access_log is None) != (not uses_log) or (uses_log and args.manifest is None):
+        raise SystemExit("Error: --access_log goes with --manifest and --placement or "
+                         "--evaluate_placement")
     src = _resolve(args.input_path)
     with open(args.tables) as fh:
         t = json.load(fh)
@@ -521,6 +534,12 @@ def main(argv=None, context: Context | None = None):
                                 t["REPLICATION_FACTORS"], args.k, context=ctx)
         rp.write_placement_csv(args.placement, res["paths"], res["factors"], res["nodes"],
                                res["node_names"])
+        print(json.dumps(dict(rp.summary_json(res["summary"]), node_names=res["node_names"])))
+    if args.evaluate_placement:
+        import replica_placement as rp
+
+        res = rp.evaluate_from_log(args.manifest, args.access_log, src, args.evaluate_placement,
+                                   categories, t["REPLICATION_FACTORS"], args.k, context=ctx)
         print(json.dumps(dict(rp.summary_json(res["summary"]), node_names=res["node_names"])))
 
 

@@ -795,6 +795,55 @@ int cdr_place_replicas(cdr_ctx* ctx, int32_t n_nodes, const int64_t* labels, int
 int cdr_place_info(cdr_ctx* ctx, int64_t* out);
 int cdr_place_timing(cdr_ctx* ctx, double* out);
 
+/* How local a GIVEN placement is under the resident events, and what it costs
+ * (the evaluation of a placement the call does not choose: yesterday's, or the
+ * block locations a cluster really has).  nodes [n_files][R] holds each file's
+ * replica nodes, entries in [-1, n_nodes), -1 = no replica.  Per file f:
+ * mask[f] = the set of its entries >= 0 (a node listed twice counts once),
+ * first[f] = its first entry >= 0 in row order (-1 without one), copies[f] =
+ * the size of the set.  An event (f, op, client) with f in [0, n_files) is
+ * local when 0 <= client < n_nodes and client is in mask[f]; events of other
+ * files are ignored; a client that is no node is never local.  op 1 = WRITE,
+ * 2 = READ (the codes of the event loaders).  All results are exact integer
+ * sums in any order of the adds.
+ *
+ * cdr_place_evaluate (extension, no reference counterpart): n_nodes in [1, 64]
+ *   and k in [1, 1024], else CDR_ERR_UNSUPPORTED; R in [1, 8].  labels:
+ *   n_labels host values in [0, k) (n_labels must be the events' n_files), or
+ *   NULL for the labels of the last assignment resident in the context (their
+ *   row count must be n_files, k >= their k).
+ *   per_file_out [n_files][2] (may be NULL) = {total, local}.  cluster_sums
+ *   [k][6], by labels[f] = {events, local, reads, reads_local, writes,
+ *   write_copies = the sum of copies[f] over the WRITE events}.  node_sums
+ *   [n_nodes][5], for node j = {issued: events with client == j, local: those
+ *   of them that are local, reads_served: the local READs of client j plus the
+ *   non-local READs of files with first[f] == j (a READ of a file with no
+ *   replica is served by nobody), writes_received: the WRITE events of files
+ *   with j in mask[f], replicas: the files with j in mask[f]}.
+ *   One pass over the files builds a 16-byte record per file; one persistent
+ *   kernel streams ev_file / ev_client / ev_op, gathers the file's record and
+ *   adds into per-workgroup LDS tables of uint64, flushed once per workgroup.
+ *   With per_file_out the kernel also adds into a uint32 [n_files][2] table;
+ *   2^32 or more resident events are CDR_ERR_UNSUPPORTED.
+ *   CDR_ERR_ARG: R out of range, a node entry or a label out of range,
+ *   n_labels other than n_files; CDR_ERR_STATE: no resident events, the event
+ *   buffers hold cdr_features_aggregate's host events, or NULL labels with
+ *   none on the device.  After any error the context stays usable.  A
+ *   successful call leaves the points, the resident and kept labels, the
+ *   grouped medians, the plan's record index, the events and the resident
+ *   partition (neither used nor dropped) as they were.
+ * cdr_place_evaluate_info (extension): out[3] = {form of the last call (0: the
+ *   event kernel without the per-file table, 1: with it, -1 none), workgroups
+ *   of the event kernel, events per workgroup and sweep}.
+ * cdr_place_evaluate_timing (extension): out[4] = {uploads and zeroing, file
+ *   pass, event kernel, copies back} ms of the last call, from HIP events. */
+int cdr_place_evaluate(cdr_ctx* ctx, int32_t n_nodes, const int32_t* nodes /* [n_files][R] */,
+                       int32_t R, const int64_t* labels, int64_t n_labels, int32_t k,
+                       int64_t* per_file_out /* [n_files][2] or NULL */,
+                       uint64_t* cluster_sums /* [k][6] */, uint64_t* node_sums /* [n_nodes][5] */);
+int cdr_place_evaluate_info(cdr_ctx* ctx, int64_t* out);
+int cdr_place_evaluate_timing(cdr_ctx* ctx, double* out);
+
 /* ---- cluster quality (extension: no reference counterpart) ------------- */
 /* Validity indices of a clustering of the resident points, for choosing the
  * k the reference fixes (src/main.py --k).  The distance is the reference's
