@@ -395,7 +395,7 @@ struct Ctx {
   bool gmed_begun = false;
   double gmed_ms[11] = {0.0};
   // timestamp range of the resident events (min, max, any null), computed by
-  // the producer that wrote them (events_ts_range, groupby.hip); valid for
+  // the producer that wrote them (events_ts_range, groupby_part.hip); valid for
   // ev_tsr_n events until another writer of ev_ts clears ev_tsr_valid
   DevBuf ev_tsr;
   bool ev_tsr_valid = false;
@@ -406,7 +406,7 @@ struct Ctx {
   DevBuf fin_counts, fin_creation, fin_out, fin_red;
   int64_t ev_n = 0, ev_nf = 0;  // resident events of cdr_features_generate
   int32_t ev_cmax = 0;          // largest client id among them (payload width)
-  // hand-written group-by (groupby.hip) scratch and what its last run did
+  // hand-written group-by (groupby.h) scratch and what its last run did
   DevBuf gb_tilepref, gb_chunk, gb_rsum, gb_part, gb_small, gb_res, gb_bbase, gb_p1, gb_p2, gb_hist2,
       gb_list, gb_slots;
   DevBuf gb_bbase3, gb_t3;  // a third partition pass (large file counts): bucket bases, tile starts

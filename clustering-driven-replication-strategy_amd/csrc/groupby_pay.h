@@ -1,12 +1,15 @@
-// groupby_pay.h — the packed event payload of the group-by's partition
-// (groupby.hip builds it, place.hip reads it again) and the record of the
-// partition a context holds.
+// groupby_pay.h — the packed event payload of the group-by's partition: its
+// layout, the one encoder (gb_make, groupby_part.hip's pass 1) and the one
+// decoder (gb_decode: the bucket kernels of groupby_bucket.hip and
+// place.hip's place_bucket), and the record of the partition a context holds.
 #pragma once
+#include <limits.h>
 #include <stdint.h>
 
 namespace cdr {
 
 constexpr int kGbMaxL = 10;  // files per bucket <= 1024
+constexpr long long kTsNullG = LLONG_MIN;
 
 // Payload layout (host-computed, passed by value):
 // [file low bits | second code | op | client code].
@@ -19,6 +22,39 @@ struct GbPay {
   long long sec_min;
   unsigned long long low_mask;  // file-low field mask (fbits - B1 bits)
 };
+
+__device__ __forceinline__ long long sec_of_g(long long ts_us) {
+  // Spark floor(cast(ts as double)); see features.hip sec_of
+  if (ts_us >= 0 && ts_us < 9000000000000000ll) return ts_us / 1000000;
+  return (long long)floor((double)ts_us / 1000000.0);
+}
+
+template <typename T>
+__device__ __forceinline__ T gb_make(const GbPay& p, unsigned flow, long long ts, uint8_t op,
+                                     int client) {
+  const unsigned long long sc = ts == kTsNullG ? ((1ull << p.sbits) - 1)
+                                               : (unsigned long long)(sec_of_g(ts) - p.sec_min);
+  const unsigned long long oc = op == 1 ? 1ull : (op == 2 ? 2ull : 0ull);
+  const unsigned long long cc = client >= 0 ? (unsigned long long)client + 1ull : 0ull;
+  return (T)(((unsigned long long)flow << p.fshift) | (sc << p.sshift) | (oc << p.cbits) | cc);
+}
+
+// The fields of one payload inside its bucket.
+struct GbFields {
+  unsigned fl;            // file-local index (the low L bits of the file field)
+  unsigned long long sc;  // second code (up to 41 bits on the hash path)
+  unsigned oc;            // 1 WRITE, 2 READ, 0 other
+  unsigned cc;            // client code: client + 1, 0 = not a node id
+};
+
+__device__ __forceinline__ GbFields gb_decode(unsigned long long v, const GbPay& p) {
+  GbFields e;
+  e.fl = (unsigned)(v >> p.fshift) & ((1u << p.L) - 1);
+  e.sc = (v >> p.sshift) & ((1ull << p.sbits) - 1);
+  e.oc = (unsigned)(v >> p.cbits) & 3u;
+  e.cc = (unsigned)v & ((1u << p.cbits) - 1);
+  return e;
+}
 
 // The resident partition: what the last groupby_resident left in the context's
 // gb_ buffers, and the events it belongs to.  Every writer of the resident

@@ -4,7 +4,7 @@
 // to the lower id), and the accesses that are node-local before and after.
 //
 //   place_bucket<T>  the bucket form: one wave owns one bucket of 2^L files of
-//                    the resident partition (groupby.hip's payload, 4 or 8 B
+//                    the resident partition (groupby_pay.h's payload, 4 or 8 B
 //                    per event), counts its events into a private LDS grid of
 //                    2^L x (n_nodes + 1) uint32 (column 0: no node), then
 //                    selects per file
@@ -217,8 +217,6 @@ __global__ __launch_bounds__(64 * kPlWaves) void place_bucket(const T* __restric
   unsigned* grid =
       reinterpret_cast<unsigned*>(pl_lds + pl_sum_words(a.k, a.n_nodes)) + (size_t)wv * KW;
   sums_clear(pl_lds, 3 * (a.k + a.n_nodes));
-  const unsigned lmask = (1u << p.L) - 1;
-  const unsigned ccmask = (1u << p.cbits) - 1;
   NodeAcc acc;
   int bad = 0;
   const int64_t nw = (int64_t)gridDim.x * kPlWaves;
@@ -249,11 +247,9 @@ __global__ __launch_bounds__(64 * kPlWaves) void place_bucket(const T* __restric
       for (int u = 0; u < kPlUnroll; ++u) {
         if (i0 + u * 64 >= n) break;  // (the same on every lane)
         if (i0 + u * 64 + lane < n) {
-          const unsigned long long x = (unsigned long long)v[u];
-          const unsigned fl = (unsigned)(x >> p.fshift) & lmask;
-          const unsigned cc = (unsigned)x & ccmask;  // client + 1, 0: no node
-          const unsigned col = cc <= (unsigned)a.n_nodes ? cc : 0u;
-          atomicAdd(&grid[fl * N1 + col], 1u);
+          const GbFields e = gb_decode((unsigned long long)v[u], p);
+          const unsigned col = e.cc <= (unsigned)a.n_nodes ? e.cc : 0u;  // (code 0: no node)
+          atomicAdd(&grid[e.fl * N1 + col], 1u);
         }
       }
     }

@@ -1,8 +1,9 @@
-"""The hand-written group-by (csrc/groupby.hip: two-level file-id partition +
-per-bucket dense (file, second) grid or LDS hash) against the independent NumPy group-by of the oracle
+"""The hand-written group-by (csrc/groupby.hip, groupby_part.hip, groupby_bucket.hip:
+two-level file-id partition + per-bucket dense (file, second) grid or LDS hash)
+against the independent NumPy group-by of the oracle
 (oracle/features_oracle.counts_from_arrays, src/compute_features.py:31-48),
 over the shapes its layout logic distinguishes: one or two partition passes,
-dense grid or hash buckets, 4- or 8-byte payloads, buckets over the LDS
+dense grid (each of its three kernels) or hash buckets, 4- or 8-byte payloads, buckets over the LDS
 capacity of either kind (redone with the global-memory hash),
 null timestamps, timestamps before the epoch, files without events, events
 outside the manifest, and a hot (file, second) pair."""
@@ -186,4 +187,57 @@ def test_register_bucket_kernel_agrees_with_ballot_kernel(ctx, monkeypatch, nf, 
     assert info["L"] <= 2, info
     monkeypatch.setenv("CDR_GB_BALLOT", "1")
     b, _ = _check(ctx, f, op, cl, ts, prim, dense=1)
+    np.testing.assert_array_equal(a, b)
+
+
+def test_block_dense_kernel_on_its_default_route(ctx):
+    """Without CDR_GB_BLOCK the block-per-bucket dense kernel runs when the
+    dense layout picks L > 8: 18 file bits, 2 second bits and ~2 events per
+    file give one pass and 512-file buckets.  The hot pair puts its bucket past
+    the events a workgroup holds in registers (the overflow loop), and with 2
+    second bits the null code 3 shares a grid word with second 2."""
+    rng = np.random.default_rng(41)
+    f, op, cl, ts, prim = _events(rng, 400_000, 200_000, span_s=3)
+    f[:3000] = 1030                       # one file, one second: concurrency 3000
+    ts[:3000] = T0 + 2_000_000 + rng.integers(0, 1_000_000, 3000)
+    f[3000:3200] = 1031                   # the same bucket: 200 null timestamps
+    ts[3000:3200] = NULL
+    got, _ = _check(ctx, f, op, cl, ts, prim, L=9, dense=1, passes=1, payload_bytes=4, big=False)
+    assert got[1030, 5] >= 3000
+    assert got[1031, 5] >= 200
+
+
+WIDE = 1 << 24  # client values: 25 client-code bits, so every dense payload takes 8 bytes
+
+
+def wide_events(seed, nf, span):
+    """200 000 events whose client codes need 25 bits; 2000 of them come from
+    their file's primary (random draws almost never hit `local`)."""
+    rng = np.random.default_rng(seed)
+    f, op, cl, ts, prim = _events(rng, 200_000, nf, span_s=span, nclients=WIDE)
+    cl[0] = WIDE - 1
+    hit = np.flatnonzero((f >= 0) & (prim[np.maximum(f, 0)] >= 0))[:2000]
+    cl[hit] = prim[f[hit]]
+    return f, op, cl, ts, prim
+
+
+def test_register_and_ballot_kernels_with_8_byte_payloads(ctx, monkeypatch):
+    """gb_bucket_wave4 (default) and gb_bucket_wave (CDR_GB_BALLOT=1) over
+    buckets of 4 files with 34-bit payloads."""
+    f, op, cl, ts, prim = wide_events(51, 2_000, 30)
+    a, _ = _check(ctx, f, op, cl, ts, prim, L=2, dense=1, payload_bytes=8)
+    assert a[:, 3].sum() > 0
+    monkeypatch.setenv("CDR_GB_BALLOT", "1")
+    b, _ = _check(ctx, f, op, cl, ts, prim, L=2, dense=1, payload_bytes=8)
+    np.testing.assert_array_equal(a, b)
+
+
+def test_wave_and_block_dense_kernels_with_8_byte_payloads(ctx, monkeypatch):
+    """gb_bucket_wave (default) and gb_bucket_dense (CDR_GB_BLOCK=1) over
+    16-file buckets after two passes with 41-bit payloads."""
+    f, op, cl, ts, prim = wide_events(52, 20_000, 200)
+    a, _ = _check(ctx, f, op, cl, ts, prim, L=4, passes=2, dense=1, payload_bytes=8)
+    assert a[:, 3].sum() > 0
+    monkeypatch.setenv("CDR_GB_BLOCK", "1")
+    b, _ = _check(ctx, f, op, cl, ts, prim, L=4, passes=2, dense=1, payload_bytes=8)
     np.testing.assert_array_equal(a, b)

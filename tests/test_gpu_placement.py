@@ -220,6 +220,24 @@ def test_eight_byte_payload(ctx):
     compare(ctx, f, cl, prim, 5, 2, [2, 5], 5, labels, form=BUCKET, payload_bytes=8)
 
 
+def test_eight_byte_payload_of_a_dense_partition(ctx):
+    """Client ids up to 2^24 (25 client-code bits) make the dense wave
+    group-by's payload 41 bits; placement reuses that partition and counts
+    every client past the nodes as no node."""
+    rng = np.random.default_rng(19)
+    nf, wide = 20_000, 1 << 24
+    f, op, cl, ts, prim = events(rng, 200_000, nf, 5, span_s=200)
+    far = rng.random(f.size) < 0.5
+    cl[far] = rng.integers(5, wide, int(far.sum()))
+    cl[0] = wide - 1
+    load(ctx, f, op, cl, ts, prim)
+    ctx.features_aggregate_resident(to_host=False)
+    gb = ctx.features_groupby_info()
+    assert (gb["hand"], gb["dense"], gb["L"], gb["passes"], gb["payload_bytes"]) == (1, 1, 4, 2, 8), gb
+    labels = rng.integers(0, 2, nf)
+    compare(ctx, f, cl, prim, 5, 2, [2, 5], 5, labels, form=BUCKET, reused=1, L=4, payload_bytes=8)
+
+
 def test_last_bucket_writes_nothing_past_n_files(ctx):
     """Guard rows after every host array keep their fill."""
     from _cdr import _check, _ptr
