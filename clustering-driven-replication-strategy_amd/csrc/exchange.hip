@@ -11,7 +11,8 @@
 // all-reduce).
 //
 // Record (16 bytes): ts int64 | file int32 (global row) | client << 8 | op
-// (client as a signed 24-bit value).
+// (client as a signed 24-bit value; the pack refuses a log with a record whose
+// client is outside [-2^23, 2^23) instead of cutting it).
 #include <algorithm>
 
 #include "cdr_internal.h"
@@ -22,6 +23,7 @@ namespace {
 
 constexpr int kXMaxRanks = 1024;
 constexpr long long kTsNullX = LLONG_MIN;
+constexpr int kXClientLim = 1 << 23;  // record clients lie in [-kXClientLim, kXClientLim)
 
 struct XRec {
   long long ts;
@@ -72,14 +74,16 @@ __global__ __launch_bounds__(256) void x_count(const int32_t* __restrict__ file,
 }
 
 // Pass 2: records into the per-rank regions (order inside a region is free:
-// the owner's group-by is order-independent).
+// the owner's group-by is order-independent).  *wide is set when a record's
+// client does not fit its 24 bits.
 __global__ __launch_bounds__(256) void x_pack(const int32_t* __restrict__ file,
                                               const uint8_t* __restrict__ op,
                                               const int32_t* __restrict__ client,
                                               const long long* __restrict__ ts, int64_t ne,
                                               const long long* __restrict__ bounds, int nr,
                                               unsigned long long* __restrict__ cursor,
-                                              XRec* __restrict__ out) {
+                                              XRec* __restrict__ out,
+                                              unsigned long long* __restrict__ wide) {
   __shared__ long long b[kXMaxRanks + 1];
   __shared__ unsigned h[kXMaxRanks];
   __shared__ unsigned long long base[kXMaxRanks];
@@ -105,7 +109,9 @@ __global__ __launch_bounds__(256) void x_pack(const int32_t* __restrict__ file,
       XRec x;
       x.ts = ts[e];
       x.file = file[e];
-      x.cop = (int32_t)(((unsigned)client[e] << 8) | op[e]);
+      const int cl = client[e];
+      if (cl < -kXClientLim || cl >= kXClientLim) *wide = 1ull;
+      x.cop = (int32_t)(((unsigned)cl << 8) | op[e]);
       out[base[r] + rk] = x;
     }
     __syncthreads();
@@ -158,13 +164,14 @@ int cdr_features_exchange_pack(cdr_ctx* h, int32_t nranks, const int64_t* bounds
   if (bounds[nranks] > c.ev_nf) CDR_FAIL(CDR_ERR_ARG, "exchange: bounds beyond the manifest");
   HIP_CHECK(hipSetDevice(c.device));
   const int64_t ne = c.ev_n;
-  c.x_small.ensure(8 * (2 * (size_t)nranks + 2) + 8 * ((size_t)nranks + 1));
+  c.x_small.ensure(8 * (2 * (size_t)nranks + 2) + 8 * ((size_t)nranks + 1));  // cnt, cur, mx, wide
   long long* dbounds = c.x_small.as<long long>();
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(dbounds + nranks + 1);
   unsigned long long* cur = cnt + nranks;
   unsigned long long* mx = cur + nranks;
+  unsigned long long* wide = mx + 1;
   HIP_CHECK(hipMemcpyAsync(dbounds, bounds, 8 * (nranks + 1), hipMemcpyHostToDevice, c.stream));
-  HIP_CHECK(hipMemsetAsync(cnt, 0, 8 * (2 * (size_t)nranks + 1), c.stream));
+  HIP_CHECK(hipMemsetAsync(cnt, 0, 8 * (2 * (size_t)nranks + 2), c.stream));
   if (ne > 0)
     hipLaunchKernelGGL(x_count, dim3(xgrid(ne)), dim3(256), 0, c.stream, c.ev_file.as<int32_t>(),
                        c.ev_ts.as<long long>(), ne, dbounds, nranks, cnt, mx);
@@ -187,8 +194,14 @@ int cdr_features_exchange_pack(cdr_ctx* h, int32_t nranks, const int64_t* bounds
     c.x_buf.ensure(sizeof(XRec) * tot);
     hipLaunchKernelGGL(x_pack, dim3(xgrid(ne)), dim3(256), 0, c.stream, c.ev_file.as<int32_t>(),
                        c.ev_op.as<uint8_t>(), c.ev_client.as<int32_t>(),
-                       c.ev_ts.as<long long>(), ne, dbounds, nranks, cur, c.x_buf.as<XRec>());
+                       c.ev_ts.as<long long>(), ne, dbounds, nranks, cur, c.x_buf.as<XRec>(),
+                       wide);
     HIP_CHECK(hipGetLastError());
+    unsigned long long hwide = 0;
+    HIP_CHECK(hipMemcpyAsync(&hwide, wide, 8, hipMemcpyDeviceToHost, c.stream));
+    HIP_CHECK(hipStreamSynchronize(c.stream));
+    if (hwide)
+      CDR_FAIL(CDR_ERR_UNSUPPORTED, "exchange: a client id outside [-2^23, 2^23) does not fit the record");
     // the caller's buffer may be host or device memory (unified addressing)
     HIP_CHECK(hipMemcpyAsync(send, c.x_buf.p, sizeof(XRec) * tot, hipMemcpyDefault, c.stream));
   }

@@ -10,7 +10,9 @@
 // Events are keyed (file << 32 | sec - sec_min), radix-sorted (radix.hip, a
 // hand-written stable LSD sort; skipped when the input is already grouped by
 // file and ordered by second, which is what the per-file Poisson generator
-// produces), then each file's run is reduced.
+// produces), then each file's run is reduced.  This is the fallback of the
+// hand-written group-by (groupby.hip) for the shapes it declines; a log that
+// spans 2^32 - 1 seconds or more is refused here (CDR_ERR_UNSUPPORTED).
 // Integer counts are exact by construction.
 //
 // K6 finalize (:53-94): age = observation_end - creation_ts_epoch (0 when the

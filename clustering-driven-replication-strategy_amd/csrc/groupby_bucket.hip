@@ -106,7 +106,7 @@ __device__ __forceinline__ void gb_event(bool act, unsigned long long v, const G
                                          const GbKey& k, unsigned long long* slots,
                                          unsigned size, bool pow2, GbFiles& g) {
   const GbFields e = gb_decode(v, p);
-  const int cl = (int)e.cc - 1;
+  const int cl = gb_client(e.cc);
   bool loc = false;
   if (act) {
     const unsigned long long cnt =
@@ -313,7 +313,7 @@ struct GbDenseTable {
     int cl = -1;
     if (act) {
       const GbFields e = gb_decode(x, p);
-      fl = e.fl, oc = e.oc, cl = (int)e.cc - 1;
+      fl = e.fl, oc = e.oc, cl = gb_client(e.cc);
       const unsigned key = (fl << p.sbits) | (unsigned)e.sc;
       atomicAdd(&grid[key >> 1], 1u << ((key & 1u) << 4));
     }
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(64 * kGwWaves) void gb_bucket_wave(
             const unsigned old = atomicAdd(&grid[key >> 1], 1u << sh);
             const unsigned cnt = ((old >> sh) & 0xFFFFu) + 1u;
             if (cnt > 1u && cnt > g.conc[e.fl]) atomicMax(&g.conc[e.fl], cnt);
-            loc = gb_local((int)e.cc - 1, g.prim[e.fl]);
+            loc = gb_local(gb_client(e.cc), g.prim[e.fl]);
           }
           gb_file_sums(g, act, e.fl, e.oc, loc, p.L);
         }
@@ -470,8 +470,9 @@ __global__ __launch_bounds__(64 * kGwWaves) void gb_bucket_wave(
 // The same for buckets of at most 4 files (L <= 2, config 4's shape): the
 // per-file count / writes / reads / local and the concurrency maximum are
 // kept in each lane's registers (select by the event's file, no ballots and
-// no per-file LDS atomics), the payload is decoded with 32-bit field
-// extracts, and the bucket's rows come from one wave reduction per value at
+// no per-file LDS atomics), a 4-byte payload is decoded with 32-bit field
+// extracts (an 8-byte one from all its 64 bits: its client code takes up to
+// 32), and the bucket's rows come from one wave reduction per value at
 // the end.  The (file, second) counts stay in the wave's LDS grid.  The
 // ballot kernel above spent ~165 instructions per 64 events here.
 template <typename T>
@@ -509,7 +510,13 @@ __global__ __launch_bounds__(64 * kGwWaves) void gb_bucket_wave4(
     // the bucket's primaries (client code = client + 1; -1: none)
     int pc[4];
 #pragma unroll
-    for (int f = 0; f < 4; ++f) pc[f] = __builtin_amdgcn_readlane(pl, f) + 1;
+    for (int f = 0; f < 4; ++f) {
+      const int q = __builtin_amdgcn_readlane(pl, f);
+      // 8-byte payloads: client codes reach 2^31 (INT_MIN as an int), so the
+      // codes compare as bit patterns and a primary below 0 takes code 0
+      if constexpr (sizeof(T) == 4) pc[f] = q + 1;
+      else pc[f] = q >= 0 ? (int)((unsigned)q + 1u) : 0;
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     unsigned A[4] = {0u, 0u, 0u, 0u}, B[4] = {0u, 0u, 0u, 0u}, M[4] = {0u, 0u, 0u, 0u};
@@ -529,14 +536,23 @@ __global__ __launch_bounds__(64 * kGwWaves) void gb_bucket_wave4(
           const unsigned lo = (unsigned)x;  // op, client and (4-byte payloads) all fields
           const unsigned fl = (unsigned)(x >> p.fshift) & (unsigned)(F - 1);
           const unsigned sc = (unsigned)(x >> p.sshift) & ((1u << sb) - 1u);
-          const unsigned oc = __builtin_amdgcn_ubfe(lo, p.cbits, 2);
-          const int cc = (int)__builtin_amdgcn_ubfe(lo, 0, p.cbits);
+          unsigned oc;
+          int cc;
+          if constexpr (sizeof(T) == 4) {  // 2 + cbits <= 32: both fields lie in lo
+            oc = __builtin_amdgcn_ubfe(lo, p.cbits, 2);
+            cc = (int)__builtin_amdgcn_ubfe(lo, 0, p.cbits);
+          } else {  // cbits up to 32: the op, or both fields, may lie past lo
+            oc = (unsigned)(x >> p.cbits) & 3u;
+            cc = (int)(unsigned)(x & ((1ull << p.cbits) - 1));
+          }
           const unsigned key = (fl << sb) | sc;
           const unsigned sh = (key & 1u) << 4;
           const unsigned old = atomicAdd(&grid[key >> 1], 1u << sh);
           const unsigned cnt = __builtin_amdgcn_ubfe(old, sh, 16) + 1u;
           const int pf = fl == 0 ? pc[0] : fl == 1 ? pc[1] : fl == 2 ? pc[2] : pc[3];
-          const unsigned loc = (cc != 0 && pf > 0 && cc == pf) ? 1u : 0u;
+          unsigned loc;
+          if constexpr (sizeof(T) == 4) loc = (cc != 0 && pf > 0 && cc == pf) ? 1u : 0u;
+          else loc = (cc != 0 && cc == pf) ? 1u : 0u;
           const unsigned va = 1u | ((oc == 1u) ? 0x10000u : 0u);
           const unsigned vb = ((oc == 2u) ? 1u : 0u) | (loc << 16);
 #pragma unroll

@@ -52,9 +52,12 @@ __device__ __forceinline__ GbFields gb_decode(unsigned long long v, const GbPay&
   e.fl = (unsigned)(v >> p.fshift) & ((1u << p.L) - 1);
   e.sc = (v >> p.sshift) & ((1ull << p.sbits) - 1);
   e.oc = (unsigned)(v >> p.cbits) & 3u;
-  e.cc = (unsigned)v & ((1u << p.cbits) - 1);
+  e.cc = (unsigned)(v & ((1ull << p.cbits) - 1));  // cbits reaches 32 (client 2^31 - 1)
   return e;
 }
+
+// The client id of a client code (-1 for code 0); code 2^31 is client 2^31 - 1.
+__device__ __forceinline__ int gb_client(unsigned cc) { return (int)(cc - 1u); }
 
 // The resident partition: what the last groupby_resident left in the context's
 // gb_ buffers, and the events it belongs to.  Every writer of the resident

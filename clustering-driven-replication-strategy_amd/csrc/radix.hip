@@ -1,7 +1,8 @@
 // radix.hip — hand-written stable LSD radix sort of (key, value) pairs, the
 // group-by's fallback for shapes its packed partition cannot hold (features.hip:
-// over ~268M files per rank, seconds beyond 2^40, (file, second) keys over 40
-// bits).  Replaces the library sort the fallback used before round 5.
+// over ~268M files per rank, payloads over 64 bits, (file, second) hash keys
+// over 40 bits; logs of up to 2^32 - 2 seconds, longer ones are refused).
+// Replaces the library sort the fallback used before round 5.
 //
 // One pass per 8-bit digit of [0, end_bit), four kernels each:
 //   rs_hist     per tile of kRsTile elements: the digit counts, stored

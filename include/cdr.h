@@ -503,7 +503,9 @@ int cdr_features_groupby_info(cdr_ctx* ctx, int64_t* info);
  * client << 8 | op int32} written to `send` (host or device memory, room for
  * every resident event); counts[r] = records for rank r; events outside the
  * manifest are not sent; *max_ts_us = max non-null timestamp over ALL
- * resident events (INT64_MIN if none) for the MAX all-reduce of :48.
+ * resident events (INT64_MIN if none) for the MAX all-reduce of :48.  The
+ * record holds the client as a signed 24-bit value: CDR_ERR_UNSUPPORTED when
+ * a record's client is outside [-2^23, 2^23).
  * cdr_features_exchange_unpack: the n records received (host or device
  * memory), all of files [file_begin, file_end), become the resident events
  * with local file ids (and the primaries of those rows move to the front).

@@ -14,7 +14,13 @@ pytestmark = pytest.mark.gpu
 PDIR = os.path.join(GOLDEN, "pipeline")
 
 
-def test_feature_counts_and_table_match_oracle(ctx):
+def test_feature_counts_and_table_match_oracle(ctx, monkeypatch):
+    """The golden log in three input orders through the hand-written group-by
+    (groupby_resident takes all of them), then the same three under
+    CDR_GROUPBY_SORT=1 through the sort fallback: as read (time-ordered: the
+    32-bit stable sort by file), shuffled (64-bit (file, second) keys, radix
+    sorted) and file-major, second-ordered (64-bit keys, already sorted: no
+    sort)."""
     import compute_features as cf
 
     paths, created, primary = cf.load_manifest(os.path.join(PDIR, "metadata.csv"))
@@ -24,14 +30,25 @@ def test_feature_counts_and_table_match_oracle(ctx):
     exp_counts, exp_mx = features_oracle.counts_from_arrays(fidx, op, cl, ts, prim, len(paths))
     np.testing.assert_array_equal(counts, exp_counts)
     assert mx == exp_mx
-    # shuffled input goes through the radix-sort path: same counts
+    assert ctx.features_groupby_info()["hand"] == 1
+    # shuffled input: same counts (the partition is order-independent)
     perm = np.random.default_rng(0).permutation(fidx.size)
     c2, mx2 = ctx.features_aggregate(fidx[perm], op[perm], cl[perm], ts[perm], prim)
     np.testing.assert_array_equal(c2, counts)
-    # file-major, second-ordered input takes the no-sort path: same counts
+    assert ctx.features_groupby_info()["hand"] == 1
+    # file-major, second-ordered input: same counts
     order = np.lexsort((ts, fidx))
     c3, _ = ctx.features_aggregate(fidx[order], op[order], cl[order], ts[order], prim)
     np.testing.assert_array_equal(c3, counts)
+    assert ctx.features_groupby_info()["hand"] == 1
+    # the same three orders through the sort fallback
+    with monkeypatch.context() as m:
+        m.setenv("CDR_GROUPBY_SORT", "1")
+        for o in (np.arange(fidx.size), perm, order):
+            cs, mxs = ctx.features_aggregate(fidx[o], op[o], cl[o], ts[o], prim)
+            assert ctx.features_groupby_info()["hand"] == 0
+            np.testing.assert_array_equal(cs, exp_counts)
+            assert mxs == exp_mx
     table = ctx.features_finalize(counts, created, mx / 1e6)
     z = np.load(os.path.join(PDIR, "features_oracle.npz"))
     np.testing.assert_array_equal(table, z["table"])
@@ -100,18 +117,20 @@ def test_main_py_flow_matches_reference(ctx):
 
 def test_generated_log_exact(ctx):
     """Device-generated, time-ordered log (the config-4 generator): the
-    resident group-by (radix sort on compact (file, second) keys) equals the
-    independent oracle counters and the host-upload path, bit for bit."""
+    resident group-by (the hand-written partition and bucket kernels) equals
+    the independent oracle counters and the host-upload path, bit for bit."""
     ne, nf = 3_000_000, 300_000
     ctx.features_generate(ne, nf, seed=1234)
     got, mx = ctx.features_aggregate_resident()
+    assert ctx.features_groupby_info()["hand"] == 1
     f, op, cl, ts, pr = ctx.features_events_read()
-    assert np.all(np.diff(ts) >= 0)  # time-ordered, so the sort path runs
+    assert np.all(np.diff(ts) >= 0)  # time-ordered, as the generator promises
     want, wmx = features_oracle.counts_from_arrays(f, op, cl, ts, pr, nf)
     np.testing.assert_array_equal(got, want)
     assert mx == wmx
     up, umx = ctx.features_aggregate(f, op, cl, ts, pr)
     np.testing.assert_array_equal(up, want)
+    assert ctx.features_groupby_info()["hand"] == 1
 
 
 def test_generated_log_config4_shard(ctx):
@@ -139,13 +158,21 @@ def test_generated_log_config4_shard(ctx):
 
 
 @pytest.mark.parametrize("ne,nf", [(0, 5), (1, 1), (2, 3), (70_000, 1)])
-def test_generated_log_edge_sizes(ctx, ne, nf):
+def test_generated_log_edge_sizes(ctx, monkeypatch, ne, nf):
     """Empty and tiny logs, a single manifest file (fbits edge) on the
-    resident path: same counters as the oracle."""
+    resident path: same counters as the oracle, from the hand-written
+    group-by and then, under CDR_GROUPBY_SORT=1, from the sort fallback."""
     ctx.features_generate(ne, nf, seed=ne + nf)
     got, mx = ctx.features_aggregate_resident()
+    assert ctx.features_groupby_info()["hand"] == 1
     f, op, cl, ts, pr = ctx.features_events_read()
     want, wmx = features_oracle.counts_from_arrays(f, op, cl, ts, pr, nf)
+    np.testing.assert_array_equal(got, want)
+    if ne:
+        assert mx == wmx
+    monkeypatch.setenv("CDR_GROUPBY_SORT", "1")
+    got, mx = ctx.features_aggregate_resident()
+    assert ctx.features_groupby_info()["hand"] == 0
     np.testing.assert_array_equal(got, want)
     if ne:
         assert mx == wmx

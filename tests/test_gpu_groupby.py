@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import event_cases as ec
 from oracle import features_oracle as fo
 
 pytestmark = pytest.mark.gpu
@@ -241,3 +242,32 @@ def test_wave_and_block_dense_kernels_with_8_byte_payloads(ctx, monkeypatch):
     monkeypatch.setenv("CDR_GB_BLOCK", "1")
     b, _ = _check(ctx, f, op, cl, ts, prim, L=4, passes=2, dense=1, payload_bytes=8)
     np.testing.assert_array_equal(a, b)
+
+
+@pytest.mark.parametrize("cmax", ec.WIDTH_CMAX)
+@pytest.mark.parametrize("kernel", list(ec.WIDTH_SHAPES))
+def test_client_ids_up_to_int32_max(ctx, monkeypatch, kernel, cmax):
+    """Client ids of 30, 31 and 32 code bits (the op field ends at bit 32, 33
+    and 34 of the 8-byte payload) through each bucket kernel's shape
+    (tests/event_cases.py width_log; tests/test_event_cases.py shows the
+    shape, a READ in it and local events through primaries of 2^30 and more).
+    Any int32 client gives the oracle's six columns, whichever route serves
+    it; where the hand-written path runs, it runs the shape's kernel."""
+    f, op, cl, ts, prim = ec.width_log(kernel, cmax)
+    switch = ec.WIDTH_SHAPES[kernel][3]
+    if switch:
+        monkeypatch.setenv(switch, "1")
+    got, mx = ctx.features_aggregate(f, op, cl, ts, prim)
+    info = ctx.features_groupby_info()
+    exp, emx = fo.counts_from_arrays(f, op, cl, ts, prim, prim.size)
+    for col, name in enumerate(["access_freq", "writes", "reads", "local_accesses",
+                                "total_accesses", "max_concurrency"]):
+        np.testing.assert_array_equal(got[:, col], exp[:, col], err_msg=name)
+    assert mx == emx
+    lay = ec.hand_layout(f, cl, ts, prim.size)
+    if lay["cbits"] == 30:
+        assert info["hand"] == 1, info
+    if info["hand"] == 1:
+        assert {k: info[k] for k in ("L", "dense", "payload_bytes", "passes")} == \
+            {k: lay[k] for k in ("L", "dense", "payload_bytes", "passes")}, info
+        assert (info["big_buckets"] > 0) == (kernel == "gb_bucket_big"), info
